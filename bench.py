@@ -15,10 +15,19 @@ every 10 rounds).  Prints ONE JSON line (rank 0).  See DESIGN.md section 5.
   python bench.py --rank-path          1 GPU through the RCCL rank path (a
                                        one-rank communicator; diagnostic)
 
-Every run first checks the sharded round against the one-shard engine on a
+A plain run sets up, warms up, times --steps rounds and prints the line.
+--dump-outputs DIR also writes what the timed rounds computed (their
+per-round stats and a fixed sample of the node rows after the last one) as
+DIR/<name>.npy, float64; the same arguments give the same inputs, so two
+builds can be compared array for array.
+
+--full adds everything else the line can carry: the CPU baseline (before the
+GPU is touched), the overlay statistics after a drain, device memory in use,
+and the sharding check -- the sharded round against the one-shard engine on a
 small churn + partition scenario (digest of every emitted record, every
 round; node rows; overlay statistics): N RCCL ranks against one GPU, or, on
 one GPU, two virtual shards against one.  A mismatch fails the run.
+--no-cpu-baseline and --no-check take single parts out of a --full run.
 """
 import argparse
 import contextlib
@@ -81,7 +90,13 @@ def parse():
     p.add_argument("--cpu-sample-rounds", type=int, default=40)
     p.add_argument("--cpu-workers", type=int, default=16,
                    help="processes of the all-cores CPU baseline (the GPU box's CPU share is 16)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline, the built-in "
+                        "sharding check, the overlay statistics after a drain, device memory in use")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write their per-round stats and a fixed sample of the node "
+                        "rows after the last one as DIR/<name>.npy (float64)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-baseline-only", action="store_true",
                    help="print the cpu_baseline object alone (no GPU): e.g. a 2^20 sample with "
                         "--cpu-sample-nodes 1048576, which takes minutes of bootstrap")
@@ -127,6 +142,46 @@ def device_mem_used_gb():
         return (tot.value - free.value) / 1e9
     except OSError:
         return None
+
+
+# -------------------------------------------------------- --dump-outputs --
+DUMP_BLOCKS, DUMP_BLOCK_NODES = 16, 256    # the node-row sample: 16 runs of 256 consecutive nodes
+DUMP_MAX_BYTES = 48 << 20                  # of the sample, as float64 (the stats add a few KB)
+DUMP_WIDE = ("digest", "have", "rng_ctr", "members_hash")   # 64-bit patterns: written as _lo / _hi halves
+
+
+def _dump_fields(out_dir, prefix, rec):
+    """Every field of a structured array as out_dir/<prefix>_<field>.npy in
+    float64 -- exact for the 32-bit fields and the counters; the 64-bit
+    patterns (DUMP_WIDE) go out as two arrays of 32-bit halves."""
+    for f in rec.dtype.names:
+        a = rec[f]
+        if f in DUMP_WIDE:
+            a = a.astype(np.uint64)
+            np.save(os.path.join(out_dir, f"{prefix}_{f}_lo.npy"), (a & np.uint64(0xFFFFFFFF)).astype(np.float64))
+            np.save(os.path.join(out_dir, f"{prefix}_{f}_hi.npy"), (a >> np.uint64(32)).astype(np.float64))
+        else:
+            np.save(os.path.join(out_dir, f"{prefix}_{f}.npy"), a.astype(np.float64))
+
+
+def dump_outputs(out_dir, stats, rows, lo, cnt):
+    """What the timed steps hand their caller: `stats`, the per-round records
+    sim.step() returned over the window, and the node rows after the last
+    round -- a sample fixed by (lo, cnt) alone: DUMP_BLOCKS runs of consecutive
+    nodes at offsets drawn from a generator seeded with 0, read through
+    rows(first, count)."""
+    os.makedirs(out_dir, exist_ok=True)
+    _dump_fields(out_dir, "stats", stats)
+    item = rows(lo, 1).dtype.itemsize * 2         # u32 -> float64
+    per = min(DUMP_BLOCK_NODES, DUMP_MAX_BYTES // (item * DUMP_BLOCKS))
+    if cnt <= DUMP_BLOCKS * per:                  # a small range: all of it
+        starts, per = np.array([lo]), cnt
+    else:
+        starts = np.sort(np.random.default_rng(0).choice(cnt // per, size=DUMP_BLOCKS, replace=False)) * per + lo
+    sample = np.concatenate([rows(int(s), per) for s in starts])
+    ids = np.concatenate([np.arange(s, s + per) for s in starts])
+    np.save(os.path.join(out_dir, "nodes_id.npy"), ids.astype(np.float64))
+    _dump_fields(out_dir, "nodes", sample)
 
 
 # ------------------------------------------------------------ launcher --
@@ -521,6 +576,8 @@ def main_strategy(args):
     st = sim.step(args.steps)
     dt = time.perf_counter() - t0
     kt = sim.kernel_times()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, st, sim.strategy_nodes, 0, n)
     msgs = int(st["emitted"].sum())
     c_ms, c_n = kt.get("consume", (0.0, 1))
     # algorithmic bytes of the consume kernel: member-row bytes it touches
@@ -581,6 +638,9 @@ def dry_run(args, world, rank, dist):
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "host_state.npy"), x.astype(np.float64))
     if rank == 0:
         print(json.dumps({"metric": "dry run (launcher test)", "value": world * args.steps / dt,
                           "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -590,6 +650,37 @@ def dry_run(args, world, rank, dist):
 
 
 # ----------------------------------------------------- HyParView (C, E) --
+def overlay_stats(sim, step, since):
+    """--full: overlay statistics (psim_get_histograms; outside the
+    measurement): drain rounds without new broadcasts until the tracked
+    (last) broadcast, `since` rounds old at the window's end, has had at
+    least its last hop + 5 rounds and OVERLAY_DRAIN rounds"""
+    step(OVERLAY_DRAIN)
+    drained = OVERLAY_DRAIN
+    while True:
+        ov = sim.histograms()
+        bins = np.arange(len(ov["hop"]))
+        last_hop = int(bins[ov["hop"] > 0].max()) if ov["delivered"] else 0
+        if since + drained >= last_hop + 5 or drained >= 400:
+            break
+        step(10)
+        drained += 10
+    nup = max(1, ov["n_up"])
+    return {
+        "nodes_up": ov["n_up"],
+        "tracked_broadcast_reliability": ov["delivered"] / nup,
+        "tracked_broadcast_last_hop": last_hop if ov["delivered"] else None,
+        "active_in_mean": float((ov["active_in"] * bins).sum() / nup),
+        "passive_in_mean": float((ov["passive_in"] * bins).sum() / nup),
+        "symmetric_active_links": ov["symmetric_links"] / max(1, ov["active_links"]),
+        "active_links": ov["active_links"],
+        "components": ov["components"],
+        "largest_component": ov["largest_component"],
+        "rounds_since_tracked_broadcast": since + drained,
+        "rounds_drained": drained,
+    }
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -614,7 +705,7 @@ def main():
                           "schedule": args.schedule, "rounds": args.cpu_sample_rounds}), flush=True)
         return
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "C":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "C":
         cpu = cpu_baseline(args)
 
     dist = None
@@ -639,7 +730,7 @@ def main():
         return obj[0]
 
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         check = shard_check(args, world, rank, dist, shared_comm())
 
     # weak scaling: --nodes per GPU; the overlay spans all GPUs, node-range
@@ -703,6 +794,10 @@ def main():
     x1 = sim.exchange_stats()
     st = np.concatenate(stats)
     dt = t1 - t0
+    if args.dump_outputs and rank == 0:
+        # (a rank reads its own node range; the stats are global)
+        per_rank = (n + world - 1) // world
+        dump_outputs(args.dump_outputs, st, sim.nodes, rank * per_rank, min(n, (rank + 1) * per_rank) - rank * per_rank)
     if world > 1:
         import torch
         t = torch.tensor([dt], dtype=torch.float64)
@@ -797,41 +892,16 @@ def main():
                            "wire_bytes_per_record": xb / max(1, xr), "record_bytes_in_memory": 64}
     if check is not None:
         out["check"] = check
-    # overlay statistics (psim_get_histograms; outside the measurement):
-    # drain rounds without new broadcasts until the tracked (last) broadcast
-    # has had at least its last hop + 5 rounds and OVERLAY_DRAIN rounds
-    since = t_start + args.steps - sched.last_bcast
-    step(OVERLAY_DRAIN)
-    drained = OVERLAY_DRAIN
-    while True:
-        ov = sim.histograms()
-        bins = np.arange(len(ov["hop"]))
-        last_hop = int(bins[ov["hop"] > 0].max()) if ov["delivered"] else 0
-        if since + drained >= last_hop + 5 or drained >= 400:
-            break
-        step(10)
-        drained += 10
-    nup = max(1, ov["n_up"])
-    out["overlay"] = {
-        "nodes_up": ov["n_up"],
-        "tracked_broadcast_reliability": ov["delivered"] / nup,
-        "tracked_broadcast_last_hop": last_hop if ov["delivered"] else None,
-        "active_in_mean": float((ov["active_in"] * bins).sum() / nup),
-        "passive_in_mean": float((ov["passive_in"] * bins).sum() / nup),
-        "symmetric_active_links": ov["symmetric_links"] / max(1, ov["active_links"]),
-        "active_links": ov["active_links"],
-        "components": ov["components"],
-        "largest_component": ov["largest_component"],
-        "rounds_since_tracked_broadcast": since + drained,
-        "rounds_drained": drained,
-    }
+    if args.full:
+        out["overlay"] = overlay_stats(sim, step, t_start + args.steps - sched.last_bcast)
     # message conservation over the window: every record emitted in round
     # r is delivered or dropped in round r + 1
     em = st["emitted"].sum(axis=1)
     got = st["delivered"].sum(axis=1) + st["dropped"]
     out["conservation"] = {"rounds_checked": int(len(st) - 1),
                            "ok": bool(np.array_equal(em[:-1], got[1:]))}
-    out["device_mem_used_gb"] = device_mem_used_gb()
+    if args.full:
+        out["device_mem_used_gb"] = device_mem_used_gb()
     out["overflow_run"] = {"rounds": sim.round, **{k: int(v) for k, v in zip(OVF_KINDS, ovf_run)},
                            "total": int(ovf_run.sum()), "strict": bool(args.strict)}
     if cpu is not None:

@@ -21,7 +21,7 @@ for e in "$@"; do
   if [ "$v" = base ]; then L=""; else L=$v; fi
   ( export PSIM_LIB=$L; IFS=','; for kv in $envs; do export "$kv"; done
     timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/t$k -o run --output-format csv -- \
-      python3 $R/bench.py --no-cpu-baseline --no-check --steps 20 --warmup 5 > $O/bench_$k.json 2> $O/bench_$k.err ) \
+      python3 $R/bench.py --full --no-cpu-baseline --no-check --steps 20 --warmup 5 > $O/bench_$k.json 2> $O/bench_$k.err ) \
     || { echo "BENCH FAILED $e"; tail -5 $O/bench_$k.err; exit 1; }
   S=$(find $O/t$k -name "*kernel_stats.csv" | head -1)
   python3 -c "

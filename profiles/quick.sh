@@ -9,7 +9,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 2
 rc=$?
 tail -2 $OUT/tests.txt
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-check > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-check > $OUT/bench.json 2> $OUT/bench.err || exit 1
 python - $OUT/bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -10,7 +10,7 @@ mkdir -p $O
 cd $R
 line() {  # name, bench args...
   local n=$1; shift
-  timeout -k 10 600 python -u bench.py --no-cpu-baseline "$@" > $O/bench_$n.json 2> $O/$n.err || { echo "$n FAILED"; tail -5 $O/$n.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full --no-cpu-baseline "$@" > $O/bench_$n.json 2> $O/$n.err || { echo "$n FAILED"; tail -5 $O/$n.err; exit 1; }
   python -c "import json; d=json.load(open('$O/bench_$n.json')); r=d['roofline']; print('$n', '%.3g' % d['value'], round(d['ms_per_step'],3), 'ms/step frac', round(r['frac'],4), 'step_frac', round(r.get('step_frac', 0) or 0,4), 'ovf', d['overflow'])"
 }
 line E26 --workload E --nodes 67108864 --steps 60 --warmup 5

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Measurement pass of the driver's bench command (python3 bench.py --gpus 1
+# Measurement pass of the driver's bench command (python3 bench.py --full --gpus 1
 # --steps 20 --warmup 5) on the GPU box, repo root: the bench line, a kernel
 # trace of the same command (per-round kernel table, host gaps), the SQ
 # counters of the node-round kernels, and the FETCH/WRITE traffic record for
@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { echo BENCH FAILED; tail -5 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { echo BENCH FAILED; tail -5 $O/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json')); r=d['roofline']; print('bench', '%.4g' % d['value'], round(d['ms_per_step'],3), 'ms/step phase', round(r['avg_launch_ms'],3), 'frac', round(r['frac'],4), 'step_frac', round(r['step_frac'],4), 'ovf', d['overflow'], 'cpu', d['cpu_baseline']['value'])"
 STEPS=20 bash profiles/prof_steady.sh $TAG/steady > /dev/null || exit 1
 gunzip -k $(find $O/steady/trace -name "*kernel_trace.csv.gz" | head -1) 2>/dev/null

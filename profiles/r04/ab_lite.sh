@@ -16,7 +16,7 @@ tail -5 $OUT/tests.txt
 [ $rc -eq 0 ] || exit $rc
 for v in half wave; do
   if [ $v = wave ]; then export PSIM_LITE_WAVE=1; else unset PSIM_LITE_WAVE; fi
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-check > $OUT/bench_$v.json 2> $OUT/bench_$v.err || exit 1
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-check > $OUT/bench_$v.json 2> $OUT/bench_$v.err || exit 1
   python - $OUT/bench_$v.json $v <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

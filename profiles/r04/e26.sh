@@ -10,7 +10,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 420 rocprofv3 --kernel-trace --stats -d $O/tr -o run --output-format csv -- \
-  python3 -u $R/bench.py --workload E --schedule doubling --nodes 67108864 --steps 60 --warmup 5 --no-cpu-baseline --no-check \
+  python3 -u $R/bench.py --full --workload E --schedule doubling --nodes 67108864 --steps 60 --warmup 5 --no-cpu-baseline --no-check \
   > $O/bench_E26.json 2> $O/E26.err || { echo "TRACE FAILED"; tail -5 $O/E26.err; exit 1; }
 T=$(find $O/tr -name "*kernel_trace.csv" | head -1)
 S=$(find $O/tr -name "*kernel_stats.csv" | head -1)
@@ -21,7 +21,7 @@ cd $R
 bash profiles/sq_kernels.sh $TAG/sq --workload E --schedule doubling --nodes 67108864 --steps 20 --warmup 5 > /dev/null || exit 1
 tail -7 gpurun_out/$TAG/sq/sq_kernels.txt
 [ "$2" = "skip-survey" ] && exit 0
-timeout -k 10 420 python3 -u bench.py --workload E --schedule survey --nodes 67108864 --steps 140 --warmup 5 --no-cpu-baseline --no-check \
+timeout -k 10 420 python3 -u bench.py --full --workload E --schedule survey --nodes 67108864 --steps 140 --warmup 5 --no-cpu-baseline --no-check \
   > $O/bench_E26s.json 2> $O/E26s.err || { echo "SURVEY E FAILED"; tail -5 $O/E26s.err; exit 1; }
 for f in bench_E26 bench_E26s; do
 python3 - $O/$f.json <<'PY'

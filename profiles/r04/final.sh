@@ -13,7 +13,7 @@ if [ "$2" != "notests" ]; then
   tail -3 $O/gpu_tests.txt
   [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
 python3 - $O/bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
@@ -22,7 +22,7 @@ print("bench %.4g node-rounds/s  ms/step %.3f  phase %.3f ms  frac %.4f  step_fr
 PY
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
-  python3 $R/bench.py --no-cpu-baseline --no-check --steps 20 --warmup 5 > $O/prof_bench.json 2> $O/prof.err || { echo PROF FAILED; tail -5 $O/prof.err; exit 1; }
+  python3 $R/bench.py --full --no-cpu-baseline --no-check --steps 20 --warmup 5 > $O/prof_bench.json 2> $O/prof.err || { echo PROF FAILED; tail -5 $O/prof.err; exit 1; }
 cd $R
 T=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv

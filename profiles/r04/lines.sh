@@ -23,7 +23,7 @@ trace() {  # name, bench args...
   local n=$1; shift
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/tr_$n -o run --output-format csv -- \
-    python3 -u $R/bench.py --no-cpu-baseline --no-check "$@" > $O/bench_$n.json 2> $O/$n.err || { echo "$n FAILED"; tail -5 $O/$n.err; exit 1; }
+    python3 -u $R/bench.py --full --no-cpu-baseline --no-check "$@" > $O/bench_$n.json 2> $O/$n.err || { echo "$n FAILED"; tail -5 $O/$n.err; exit 1; }
   cd $R
   cp $(find $O/tr_$n -name "*kernel_stats.csv" | head -1) $O/kernel_stats_$n.csv
   local T=$(find $O/tr_$n -name "*kernel_trace.csv" | head -1)
@@ -42,9 +42,9 @@ bash profiles/run_pmc.sh ${TAG}_E26s $E26S --no-check | tail -1 || exit 1
 bash profiles/run_pmc.sh ${TAG}_B --workload B --steps 20 --warmup 5 | tail -1 || exit 1
 bash profiles/run_pmc.sh ${TAG}_D --workload D --steps 20 --warmup 5 | tail -1 || exit 1
 bash profiles/run_pmc.sh ${TAG}_C24 --nodes 16777216 --steps 20 --warmup 5 --no-check | tail -1 || exit 1
-for n in B D; do timeout -k 10 300 python3 bench.py --no-cpu-baseline --workload $n --steps 20 --warmup 5 > $O/bench_$n.json 2> $O/$n.err && summ $O/bench_$n.json; done
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-check --nodes 16777216 --steps 20 --warmup 5 > $O/bench_C24.json 2> $O/C24.err && summ $O/bench_C24.json
-timeout -k 10 600 python3 bench.py --no-cpu-baseline --no-check $E26S > $O/bench_E26s_pmc.json 2> $O/E26s_pmc.err && summ $O/bench_E26s_pmc.json
+for n in B D; do timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --workload $n --steps 20 --warmup 5 > $O/bench_$n.json 2> $O/$n.err && summ $O/bench_$n.json; done
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-check --nodes 16777216 --steps 20 --warmup 5 > $O/bench_C24.json 2> $O/C24.err && summ $O/bench_C24.json
+timeout -k 10 600 python3 bench.py --full --no-cpu-baseline --no-check $E26S > $O/bench_E26s_pmc.json 2> $O/E26s_pmc.err && summ $O/bench_E26s_pmc.json
 bash profiles/sq_kernels.sh $TAG/sq_E26 --workload E --schedule survey --nodes 67108864 --steps 20 --warmup 5 > /dev/null && tail -7 $O/sq_E26/sq_kernels.txt
 timeout -k 10 600 python3 -u tests/c_overlay.py --backend gpu --nodes 1048576 > $O/c_overlay_gpu.jsonl 2>&1
 timeout -k 10 900 python3 -u tests/c_overlay.py --backend gpu --nodes 16777216 --points > $O/c_overlay_gpu24.jsonl 2>&1

@@ -8,8 +8,8 @@ E26S="--workload E --schedule survey --nodes 67108864 --steps 140 --warmup 5"
 bash profiles/run_pmc.sh ${TAG}_B --workload B --steps 20 --warmup 5 | tail -1 || exit 1
 bash profiles/run_pmc.sh ${TAG}_D --workload D --steps 20 --warmup 5 | tail -1 || exit 1
 bash profiles/run_pmc.sh ${TAG}_E26s $E26S --no-check | tail -1 || exit 1
-for n in B D; do timeout -k 10 300 python3 bench.py --no-cpu-baseline --workload $n --steps 20 --warmup 5 > $O/bench_$n.json 2> $O/$n.err || exit 1; done
-timeout -k 10 600 python3 bench.py --no-cpu-baseline --no-check $E26S > $O/bench_E26s.json 2> $O/E26s.err || exit 1
+for n in B D; do timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --workload $n --steps 20 --warmup 5 > $O/bench_$n.json 2> $O/$n.err || exit 1; done
+timeout -k 10 600 python3 bench.py --full --no-cpu-baseline --no-check $E26S > $O/bench_E26s.json 2> $O/E26s.err || exit 1
 for f in $O/bench_*.json; do python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d['roofline']

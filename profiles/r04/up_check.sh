@@ -11,7 +11,7 @@ tail -2 $O/tests.txt; [ $rc -eq 0 ] || exit $rc
 bash profiles/r04/ab_env.sh $TAG "base:" || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace -d $O/tr -o run --output-format csv -- \
-  python3 -u $R/bench.py --no-cpu-baseline --no-check --workload E --schedule doubling --nodes 67108864 --steps 60 --warmup 5 \
+  python3 -u $R/bench.py --full --no-cpu-baseline --no-check --workload E --schedule doubling --nodes 67108864 --steps 60 --warmup 5 \
   > $O/bench_E26d.json 2> $O/E26d.err || { echo "E26 FAILED"; tail -5 $O/E26d.err; exit 1; }
 cd $R
 python3 profiles/round_kernels.py $(find $O/tr -name "*kernel_trace.csv" | head -1) 60 --tail 40 > $O/kernels_E26d.txt; rm -rf $O/tr

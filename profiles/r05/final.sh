@@ -14,7 +14,7 @@ if [ "$2" != "notests" ]; then
   tail -3 $O/gpu_tests.txt
   [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
 python3 - $O/bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
@@ -23,7 +23,7 @@ print("bench %.4g node-rounds/s  ms/step %.3f  phase %.3f ms  frac %.4f  step_fr
 PY
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
-  python3 $R/bench.py --no-cpu-baseline --no-check --steps 20 --warmup 5 > $O/prof_bench.json 2> $O/prof.err || { echo PROF FAILED; tail -5 $O/prof.err; exit 1; }
+  python3 $R/bench.py --full --no-cpu-baseline --no-check --steps 20 --warmup 5 > $O/prof_bench.json 2> $O/prof.err || { echo PROF FAILED; tail -5 $O/prof.err; exit 1; }
 cd $R
 T=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
@@ -34,6 +34,6 @@ bash profiles/sq_kernels.sh $TAG/sq --steps 20 --warmup 5 > /dev/null || exit 1
 tail -8 $O/sq/sq_kernels.txt
 bash profiles/run_pmc.sh $TAG --steps 20 --warmup 5 --no-check | tail -1
 [ -f partisan_amd/csrc/libpartisan_gpu_sim_stamps.so ] && PSIM_LIB=stamps timeout -k 10 300 python3 profiles/stamps.py --steps 20 > $O/stamps.txt 2>&1 && tail -12 $O/stamps.txt
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -3 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -3 $O/bench_default.err; exit 1; }
 bash profiles/e26b.sh $TAG/e26 --strict > $O/e26.txt 2>&1; head -3 $O/e26.txt
 echo ALL DONE

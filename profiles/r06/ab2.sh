@@ -17,7 +17,7 @@ if [ -n "$CV" ]; then bash profiles/abn.sh $TAG $ROUNDS $CV || exit 1; fi
 for v in $EV; do
   E=""
   if [ "$v" = base ]; then L=""; elif [[ "$v" == *=* ]]; then L=""; E=${v//,/ }; else L=$v; fi
-  env $E PSIM_LIB=$L timeout -k 10 600 python -u bench.py --workload E --nodes 67108864 --steps 140 --warmup 5 \
+  env $E PSIM_LIB=$L timeout -k 10 600 python -u bench.py --full --workload E --nodes 67108864 --steps 140 --warmup 5 \
       --no-cpu-baseline --strict > $O/e26_$v.json 2> $O/e26_$v.err || { echo "E26 FAILED $v"; tail -5 $O/e26_$v.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/e26_$v.json')); r=d['roofline']; print('E26 $v', '%.4g' % d['value'], round(d['ms_per_step'],3), 'ms/step phase', round(r['avg_launch_ms'],3), 'mem', d['device_mem_used_gb'], 'ovf', d['overflow_run']['total'])"
 done

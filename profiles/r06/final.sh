@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
 python3 - $O/bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
@@ -19,7 +19,7 @@ print("bench %.4g node-rounds/s  ms/step %.4f  phase %.4f ms  frac %.4f  step_fr
 PY
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
-  python3 $R/bench.py --no-cpu-baseline --no-check --steps 20 --warmup 5 > $O/prof_bench.json 2> $O/prof.err || { echo PROF FAILED; tail -5 $O/prof.err; exit 1; }
+  python3 $R/bench.py --full --no-cpu-baseline --no-check --steps 20 --warmup 5 > $O/prof_bench.json 2> $O/prof.err || { echo PROF FAILED; tail -5 $O/prof.err; exit 1; }
 cd $R
 T=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
@@ -30,5 +30,5 @@ bash profiles/sq_kernels.sh $TAG/sq --steps 20 --warmup 5 > /dev/null || exit 1
 tail -8 $O/sq/sq_kernels.txt
 bash profiles/run_pmc.sh $TAG --steps 20 --warmup 5 --no-check | tail -1
 [ -f partisan_amd/csrc/libpartisan_gpu_sim_stamps.so ] && PSIM_LIB=stamps timeout -k 10 300 python3 profiles/stamps.py --steps 20 > $O/stamps.txt 2>&1 && tail -12 $O/stamps.txt
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -3 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -3 $O/bench_default.err; exit 1; }
 echo ALL DONE

@@ -8,6 +8,6 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 cd $R
 bash profiles/r06/final.sh $TAG || exit 1
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --rank-path --no-cpu-baseline > $O/bench_rank.json 2> $O/bench_rank.err || { tail -5 $O/bench_rank.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --rank-path --no-cpu-baseline > $O/bench_rank.json 2> $O/bench_rank.err || { tail -5 $O/bench_rank.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/bench_rank.json')); print('rank', '%.4g' % d['value'], round(d['ms_per_step'], 4), 'ms/step')"
 echo FINAL2 DONE

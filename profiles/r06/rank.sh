@@ -9,8 +9,8 @@ cd $R
 timeout -k 10 600 python -u -m pytest tests/test_rccl1.py tests/test_loopback.py tests/test_gpu_knobs.py -x -q --timeout 300 --timeout-method thread > $O/rank_tests.txt 2>&1; rc=$?
 tail -3 $O/rank_tests.txt
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --rank-path --no-cpu-baseline > $O/bench_rank.json 2> $O/bench_rank.err || { tail -5 $O/bench_rank.err; exit 1; }
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --rank-path --no-cpu-baseline > $O/bench_rank.json 2> $O/bench_rank.err || { tail -5 $O/bench_rank.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python3 - $O <<'PY'
 import json, sys
 for f in ("bench_rank.json", "bench.json"):

@@ -7,11 +7,11 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-PSIM_TRACE_BATCH=1 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --rank-path --no-cpu-baseline > $O/bench_rank.json 2> $O/bench_rank.err || { tail -5 $O/bench_rank.err; exit 1; }
+PSIM_TRACE_BATCH=1 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --rank-path --no-cpu-baseline > $O/bench_rank.json 2> $O/bench_rank.err || { tail -5 $O/bench_rank.err; exit 1; }
 grep "batch of" $O/bench_rank.err | tail -12
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
-  python3 $R/bench.py --no-cpu-baseline --no-check --steps 20 --warmup 5 --rank-path > $O/prof_rank.json 2> $O/prof_rank.err || { echo PROF FAILED; tail -5 $O/prof_rank.err; exit 1; }
+  python3 $R/bench.py --full --no-cpu-baseline --no-check --steps 20 --warmup 5 --rank-path > $O/prof_rank.json 2> $O/prof_rank.err || { echo PROF FAILED; tail -5 $O/prof_rank.err; exit 1; }
 cd $R
 T=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 TAIL=$(python3 -c "import json,sys; print(json.load(open(sys.argv[1]))['overlay']['rounds_drained'])" $O/prof_rank.json)

@@ -8,9 +8,9 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
-    python3 $R/bench.py --no-cpu-baseline "$@" > $OUT/bench.json
+    python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/bench.json
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o run --output-format csv -- \
-    python3 $R/bench.py --no-cpu-baseline "$@" > $OUT/bench_fetch.json
+    python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/bench_fetch.json
 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -o run --output-format csv -- \
-    python3 $R/bench.py --no-cpu-baseline "$@" > $OUT/bench_write.json
+    python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/bench_write.json
 echo profile done
