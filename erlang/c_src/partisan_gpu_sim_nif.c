@@ -340,6 +340,38 @@ static ERL_NIF_TERM nif_histograms(ErlNifEnv *env, int argc, const ERL_NIF_TERM 
     return enif_make_tuple2(env, enif_make_atom(env, "ok"), m);
 }
 
+/* strategy_histograms(Ref) -> {ok, #{...}} : overlay statistics of a
+ * pluggable handle (psim_strategy_histograms) */
+static ERL_NIF_TERM nif_strategy_histograms(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+    sim_res *r;
+    psim_strategy_histograms hs;
+    if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r)) return enif_make_badarg(env);
+    enif_mutex_lock(r->mu);
+    int rc = psim_get_strategy_histograms(r->h, &hs);
+    enif_mutex_unlock(r->mu);
+    if (rc) return err(env, rc);
+    const uint64_t *bins[4] = {hs.view_fill, hs.in_fill, hs.out_degree, hs.in_degree};
+    const char *bnames[4] = {"view_fill", "in_fill", "out_degree", "in_degree"};
+    ERL_NIF_TERM m = enif_make_new_map(env);
+    for (int k = 0; k < 4; k++) {
+        ERL_NIF_TERM v[PSIM_HIST_BINS];
+        for (int b = 0; b < PSIM_HIST_BINS; b++) v[b] = enif_make_uint64(env, bins[k][b]);
+        enif_make_map_put(env, m, enif_make_atom(env, bnames[k]),
+                          enif_make_list_from_array(env, v, PSIM_HIST_BINS), &m);
+    }
+    const char *snames[20] = {"n_up", "view_sum", "in_sum", "view_max", "in_degree_max", "links", "mutual_links",
+                              "dangling_links", "self_entries", "duplicate_entries", "in_view_links",
+                              "in_view_confirmed", "components", "largest_component", "isolated", "members_min",
+                              "members_max", "members_sum", "agreeing", NULL};
+    const uint64_t svals[20] = {hs.n_up, hs.view_sum, hs.in_sum, hs.view_max, hs.in_degree_max, hs.links,
+                                hs.mutual_links, hs.dangling_links, hs.self_entries, hs.duplicate_entries,
+                                hs.in_view_links, hs.in_view_confirmed, hs.components, hs.largest_component,
+                                hs.isolated, hs.members_min, hs.members_max, hs.members_sum, hs.agreeing, 0};
+    for (int k = 0; snames[k]; k++)
+        enif_make_map_put(env, m, enif_make_atom(env, snames[k]), enif_make_uint64(env, svals[k]), &m);
+    return enif_make_tuple2(env, enif_make_atom(env, "ok"), m);
+}
+
 /* snapshot(Ref) -> {ok, Binary} ; restore(Ref, Binary) -> ok */
 static ERL_NIF_TERM nif_snapshot(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
     sim_res *r;
@@ -474,6 +506,7 @@ static ErlNifFunc funcs[] = {
     {"members_nif", 3, nif_members, 0},
     {"delivery_nif", 2, nif_delivery, 0},
     {"histograms", 1, nif_histograms, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"strategy_histograms", 1, nif_strategy_histograms, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"set_partition_nif", 2, nif_set_partition, 0},
     {"clear_partition_nif", 1, nif_clear_partition, 0},
     {"set_bucket_table_nif", 2, nif_set_bucket_table, 0},

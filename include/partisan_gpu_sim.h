@@ -317,6 +317,41 @@ typedef struct psim_histograms {
     uint64_t reserved[6];
 } psim_histograms;
 
+/* Overlay statistics of a PLUGGABLE handle (SCAMP
+ * beside HyParView), computed on the device from a compact CSR of the whole
+ * overlay (DESIGN.md "Overlay statistics of pluggable handles").  Binning as
+ * psim_histograms: bin k = value k, the last bin = PSIM_HIST_BINS - 1 or
+ * more.  A link is a distinct ordered pair: an id held twice by a view counts
+ * once.
+ *   SCAMP v1 / v2 handles: members_* and agreeing stay zero; the in_view
+ *     fields (in_fill, in_sum, in_view_links, in_view_confirmed) are v2's
+ *     and zero under v1.
+ *   full handles: only n_up, members_* and agreeing are filled; every view,
+ *     link and component field stays zero (the strategy keeps no partial
+ *     view: its overlay is the member set itself). */
+typedef struct psim_strategy_histograms {
+    uint64_t n_up;                              /* live nodes */
+    uint64_t view_fill[PSIM_HIST_BINS];         /* live nodes by view_n: the raw list length the strategy
+                                                   itself sees, self and repeats included */
+    uint64_t in_fill[PSIM_HIST_BINS];           /* scamp v2: live nodes by in_n; zero otherwise */
+    uint64_t out_degree[PSIM_HIST_BINS];        /* live nodes by distinct ids != self in their view (live or not) */
+    uint64_t in_degree[PSIM_HIST_BINS];         /* live nodes by distinct live nodes != self whose view holds them */
+    uint64_t view_sum, in_sum;                  /* sums of view_n / in_n over live nodes (exact means past the last bin) */
+    uint64_t view_max, in_degree_max;
+    uint64_t links;                             /* distinct directed pairs i->p, i != p, both live */
+    uint64_t mutual_links;                      /* ... of which p->i is also a link */
+    uint64_t dangling_links;                    /* distinct pairs i->p, i live, p != i not live */
+    uint64_t self_entries;                      /* live nodes whose view holds themselves */
+    uint64_t duplicate_entries;                 /* view entries of live nodes beyond the first occurrence of their id */
+    uint64_t in_view_links, in_view_confirmed;  /* scamp v2: distinct (i, j), j in i's in_view, j != i, both live;
+                                                   ... of which j->i is a link */
+    uint64_t components, largest_component;     /* weakly connected components of live nodes over `links` */
+    uint64_t isolated;                          /* live nodes with no link in or out */
+    uint64_t members_min, members_max, members_sum;  /* full: |query(ORSet)| = popcount(add & ~remove) over live nodes */
+    uint64_t agreeing;                          /* full: live nodes whose member set equals that of the lowest live id */
+    uint64_t reserved[8];
+} psim_strategy_histograms;
+
 typedef struct psim_handle psim_handle;
 
 void psim_default_config(psim_config *cfg);
@@ -447,6 +482,13 @@ int psim_get_delivery(psim_handle *h, uint32_t first, uint32_t count, uint8_t *h
  * sharded handles gather every node's active row first (device copies, or an
  * ncclAllGather across RCCL ranks -- a collective: every rank must call). */
 int psim_get_histograms(psim_handle *h, psim_histograms *out);
+/* Overlay statistics of a pluggable handle (psim_strategy_histograms above).
+ * PSIM_EINVAL for a null argument, PSIM_EUNSUPPORTED for HyParView and X-BOT
+ * handles (psim_get_histograms is theirs).  Only the reduced counters come
+ * back to the host.  Read-only: the rounds stepped after it are those of a
+ * run without it.  Like psim_get_histograms a collective on rank handles
+ * (every rank must call; every rank gets the same struct). */
+int psim_get_strategy_histograms(psim_handle *h, psim_strategy_histograms *out);
 /* Snapshot of the whole simulation state of this process (node rows,
  * in-flight messages, round, events not yet applied are not included):
  * with buf == NULL (or cap too small) only *need is set.  psim_restore

@@ -119,6 +119,23 @@ class PsimHistograms(C.Structure):
     ]
 
 
+class PsimStrategyHistograms(C.Structure):
+    _fields_ = [
+        ("n_up", C.c_uint64),
+        ("view_fill", C.c_uint64 * HIST_BINS), ("in_fill", C.c_uint64 * HIST_BINS),
+        ("out_degree", C.c_uint64 * HIST_BINS), ("in_degree", C.c_uint64 * HIST_BINS),
+        ("view_sum", C.c_uint64), ("in_sum", C.c_uint64),
+        ("view_max", C.c_uint64), ("in_degree_max", C.c_uint64),
+        ("links", C.c_uint64), ("mutual_links", C.c_uint64), ("dangling_links", C.c_uint64),
+        ("self_entries", C.c_uint64), ("duplicate_entries", C.c_uint64),
+        ("in_view_links", C.c_uint64), ("in_view_confirmed", C.c_uint64),
+        ("components", C.c_uint64), ("largest_component", C.c_uint64), ("isolated", C.c_uint64),
+        ("members_min", C.c_uint64), ("members_max", C.c_uint64), ("members_sum", C.c_uint64),
+        ("agreeing", C.c_uint64),
+        ("reserved", C.c_uint64 * 8),
+    ]
+
+
 NODE_VIEW_DTYPE = np.dtype(PsimNodeView)
 STRATEGY_VIEW_DTYPE = np.dtype(PsimStrategyView)
 STATS_DTYPE = np.dtype(PsimRoundStats)
@@ -166,6 +183,8 @@ GPU_ONLY = {
     "restore": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
     "get_exchange_stats": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "debug_kernel_counts": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int]),
+    # (no oracle twin: the tests' reference is numpy over the oracle's views)
+    "get_strategy_histograms": (C.c_int, [_H, C.POINTER(PsimStrategyHistograms)]),
 }
 
 

@@ -37,6 +37,7 @@
 #include "psim_comm.h"
 #include "psim_device.h"
 #include "psim_kernels.h"
+#include "psim_wave.h"
 
 using namespace psim;
 
@@ -1716,12 +1717,16 @@ __global__ void k_cc_init(const uint8_t* __restrict__ flags, uint32_t n, uint32_
     if (i < n) L[i] = (flags[i] & F_UP) ? i : PSIM_NONE;
 }
 
-__global__ void k_cc_hook(const uint8_t* __restrict__ gan, const uint32_t* __restrict__ act,
-                          const uint8_t* __restrict__ flags, uint32_t n, uint32_t* L, uint32_t* changed) {
+// (node i's row: gan[i] ids at act + off[i] -- a CSR, the pluggable handles'
+// overlay -- or, off == nullptr, at act + i * PSIM_ACTIVE_CAP: HyParView's rows)
+__global__ void k_cc_hook(const uint32_t* __restrict__ off, const uint8_t* __restrict__ gan,
+                          const uint32_t* __restrict__ act, const uint8_t* __restrict__ flags, uint32_t n,
+                          uint32_t* L, uint32_t* changed) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !(flags[i] & F_UP)) return;
+    const uint32_t* row = act + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP);
     for (uint32_t k = 0; k < gan[i]; k++) {
-        const uint32_t p = act[(size_t)i * PSIM_ACTIVE_CAP + k];
+        const uint32_t p = row[k];
         if (p == i || p >= n || !(flags[p] & F_UP)) continue;
         const uint32_t a = L[i], b = L[p];
         if (a < b) { if (atomicMin(&L[p], a) > a) *changed = 1; }
@@ -1747,6 +1752,261 @@ __global__ void k_cc_count(const uint32_t* __restrict__ L, uint32_t n, uint32_t*
 __global__ void k_cc_max(const uint32_t* __restrict__ size, uint32_t n, unsigned long long* largest) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && size[i]) atomicMax(largest, (unsigned long long)size[i]);
+}
+
+// ------------------------------------------ overlay stats, pluggable --
+// psim_get_strategy_histograms.  A SCAMP row is PSIM_SVIEW_CAP ids with ~3 in
+// use, so the whole overlay is packed into a CSR instead of gathering rows:
+//   k_sh_rows (count)  a wave takes 64 local nodes and holds one view at a time
+//                      as two 64-lane registers (only the lanes below its
+//                      length load), marks
+//                      first occurrences, self and live targets, counts the
+//                      per-node statistics and writes the node's number of
+//                      distinct live targets != self (a byte, by global id)
+//   scan_excl          the counts (all-gathered across ranks) -> row offsets
+//   k_sh_rows (pack)   the same wave writes those targets at its offset
+//   k_sh_links / k_sh_in / k_sh_inv / k_cc_*   statistics over the CSR
+// sl layout (summed over ranks; SL_VMAX: max): three histograms, then scalars
+enum { SL_VFILL = 0, SL_IFILL = 1, SL_OUT = 2, SL_NUP = 3 * PSIM_HIST_BINS, SL_VSUM, SL_ISUM, SL_DANG, SL_SELF,
+       SL_DUP, SL_IVL, SL_IVC, SL_VMAX, SL_N };
+// sg layout (over the whole CSR, the same on every rank): the in-degree
+// histogram, then scalars
+enum { SG_LINKS = PSIM_HIST_BINS, SG_MUTUAL, SG_INMAX, SG_ISOL, SG_COMPS, SG_LARGEST, SG_N };
+// full strategy
+enum { SF_NUP = 0, SF_MIN, SF_MAX, SF_SUM, SF_AGREE, SF_N };
+constexpr uint32_t SH_NPB = BLK;      // nodes a k_sh_rows / k_sh_inv block takes: 64 a wave
+
+// a row of n <= PSIM_SVIEW_CAP ids, entry l in lane l of `a`, entry 64 + l in
+// lane l of `b` (lanes past n: PSIM_NONE, never loaded)
+DEV void sh_row_load(const uint32_t* __restrict__ row, uint32_t n, uint32_t& a, uint32_t& b) {
+    const uint32_t l = lane_id();
+    a = l < n ? row[l] : PSIM_NONE;
+    b = n > 64 && 64 + l < n ? row[64 + l] : PSIM_NONE;
+}
+// fa / fb: the lane's entry is the first occurrence of its id in the row
+DEV void sh_row_first(uint32_t a, uint32_t b, uint32_t n, bool& fa, bool& fb) {
+    const uint32_t l = lane_id();
+    fa = l < n; fb = 64 + l < n;
+    for (uint32_t j = 0; j + 1 < n; j++) {            // (uniform: n is)
+        const uint32_t v = j < 64 ? shfl(a, (int)j) : shfl(b, (int)(j - 64));
+        if (l > j && a == v) fa = false;
+        if (64 + l > j && b == v) fb = false;
+    }
+}
+DEV uint32_t sh_wave_sum(uint32_t v) {
+    for (int d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    return v;
+}
+DEV bool sh_live(const uint8_t* __restrict__ flags, uint32_t N, uint32_t id) {
+    return id < N && (flags[id] & F_UP);
+}
+
+// off == nullptr: the count pass (statistics into sl, the node's link count
+// into cnt[lo + i]); else the pack pass (the links into adj at off[lo + i])
+__global__ void __launch_bounds__(BLK) k_sh_rows(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ sview,
+                                                 const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n,
+                                                 uint32_t N, uint32_t v2, uint8_t* cnt,
+                                                 const uint32_t* __restrict__ off, uint32_t* adj,
+                                                 unsigned long long* sl) {
+    __shared__ unsigned long long sh[SL_N];
+    for (uint32_t j = threadIdx.x; j < SL_N; j += blockDim.x) sh[j] = 0;
+    __syncthreads();
+    const uint32_t l = lane_id();
+    const uint32_t base = blockIdx.x * SH_NPB + (threadIdx.x >> 6) * 64;     // this wave's first node
+    const uint32_t mine = base + l;
+    uint32_t vn = 0, in_n = 0, o = 0, my_cnt = 0;
+    if (mine < n && (flags[lo + mine] & F_UP)) {
+        vn = min((uint32_t)hdr[mine].act_n, (uint32_t)PSIM_SVIEW_CAP);
+        in_n = hdr[mine].pas_n;
+        if (off) o = off[lo + mine];
+    }
+    const uint64_t up = ballot(mine < n && (flags[lo + mine] & F_UP));
+    uint64_t todo = off ? ballot(vn != 0) : up;
+    unsigned long long s_vsum = 0, s_isum = 0, s_dang = 0, s_self = 0, s_dup = 0, s_vmax = 0;
+    while (todo) {                                    // (uniform)
+        const int k = ffs64(todo);
+        todo &= todo - 1;
+        const uint32_t i = base + (uint32_t)k, me = lo + i;
+        const uint32_t len = shfl(vn, k);
+        uint32_t a, b;
+        bool fa, fb;
+        sh_row_load(sview + (size_t)i * PSIM_SVIEW_CAP, len, a, b);
+        sh_row_first(a, b, len, fa, fb);
+        const uint64_t oa = ballot(fa && a != me), ob = ballot(fb && b != me);
+        const uint64_t la = ballot(fa && a != me && sh_live(flags, N, a));
+        const uint64_t lb = ballot(fb && b != me && sh_live(flags, N, b));
+        if (off) {
+            const uint32_t at = shfl(o, k);
+            if ((la >> l) & 1) adj[at + popc(la & lt_mask())] = a;
+            if ((lb >> l) & 1) adj[at + popc(la) + popc(lb & lt_mask())] = b;
+            continue;
+        }
+        const uint32_t links = popc(la) + popc(lb), others = popc(oa) + popc(ob);
+        const uint32_t distinct = popc(ballot(fa)) + popc(ballot(fb));
+        if (l == (uint32_t)k) my_cnt = links;
+        s_vsum += len; s_dang += others - links; s_self += distinct - others; s_dup += len - distinct;
+        s_vmax = len > s_vmax ? len : s_vmax;
+        const uint32_t inn = v2 ? shfl(in_n, k) : 0;
+        s_isum += inn;
+        if (l == 0) {
+            atomicAdd(&sh[SL_VFILL * PSIM_HIST_BINS + hbin(len)], 1ull);
+            atomicAdd(&sh[SL_OUT * PSIM_HIST_BINS + hbin(others)], 1ull);
+            if (v2) atomicAdd(&sh[SL_IFILL * PSIM_HIST_BINS + hbin(inn)], 1ull);
+        }
+    }
+    if (off) return;
+    if (mine < n) cnt[lo + mine] = (uint8_t)my_cnt;
+    if (l == 0) {
+        atomicAdd(&sh[SL_NUP], (unsigned long long)popc(up));
+        atomicAdd(&sh[SL_VSUM], s_vsum); atomicAdd(&sh[SL_ISUM], s_isum); atomicAdd(&sh[SL_DANG], s_dang);
+        atomicAdd(&sh[SL_SELF], s_self); atomicAdd(&sh[SL_DUP], s_dup); atomicMax(&sh[SL_VMAX], s_vmax);
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < SL_N; j += blockDim.x) {
+        if (!sh[j]) continue;
+        if (j == SL_VMAX) atomicMax(&sl[j], sh[j]);
+        else atomicAdd(&sl[j], sh[j]);
+    }
+}
+
+// is `id` in node p's CSR row?
+DEV bool sh_has(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt, const uint32_t* __restrict__ adj,
+                uint32_t p, uint32_t id) {
+    const uint32_t* row = adj + off[p];
+    for (uint32_t q = 0, c = cnt[p]; q < c; q++)
+        if (row[q] == id) return true;
+    return false;
+}
+
+// scamp v2: the in_view rows of the local nodes against the CSR -- the
+// distinct live (i, j != i) with j in i's in_view, and those with j -> i a link
+__global__ void __launch_bounds__(BLK) k_sh_inv(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ sinv,
+                                                const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n,
+                                                uint32_t N, const uint32_t* __restrict__ off,
+                                                const uint8_t* __restrict__ cnt, const uint32_t* __restrict__ adj,
+                                                unsigned long long* sl) {
+    const uint32_t l = lane_id();
+    const uint32_t base = blockIdx.x * SH_NPB + (threadIdx.x >> 6) * 64;
+    const uint32_t mine = base + l;
+    uint32_t in_n = 0;
+    if (mine < n && (flags[lo + mine] & F_UP)) in_n = min((uint32_t)hdr[mine].pas_n, (uint32_t)PSIM_SVIEW_CAP);
+    uint64_t todo = ballot(in_n != 0);
+    uint32_t ivl = 0, ivc = 0;                        // (per lane)
+    while (todo) {                                    // (uniform)
+        const int k = ffs64(todo);
+        todo &= todo - 1;
+        const uint32_t i = base + (uint32_t)k, me = lo + i;
+        const uint32_t len = shfl(in_n, k);
+        uint32_t a, b;
+        bool fa, fb;
+        sh_row_load(sinv + (size_t)i * PSIM_SVIEW_CAP, len, a, b);
+        sh_row_first(a, b, len, fa, fb);
+        if (fa && a != me && sh_live(flags, N, a)) { ivl++; ivc += sh_has(off, cnt, adj, a, me) ? 1u : 0u; }
+        if (fb && b != me && sh_live(flags, N, b)) { ivl++; ivc += sh_has(off, cnt, adj, b, me) ? 1u : 0u; }
+    }
+    ivl = sh_wave_sum(ivl); ivc = sh_wave_sum(ivc);
+    if (l == 0 && ivl) atomicAdd(&sl[SL_IVL], (unsigned long long)ivl);
+    if (l == 0 && ivc) atomicAdd(&sl[SL_IVC], (unsigned long long)ivc);
+}
+
+// per rank r (one thread): its first row offset base[r] = E[r * per] and, in
+// tot[0], the largest number of links a rank holds (E: the exclusive scan of
+// the counts, npad + 1 entries)
+__global__ void k_sh_rank_tot(const uint32_t* __restrict__ E, uint32_t per, uint32_t W, uint32_t npad,
+                              uint32_t* base, unsigned long long* tot) {
+    if (blockIdx.x || threadIdx.x) return;
+    unsigned long long mx = 0;
+    for (uint32_t r = 0; r < W; r++) {
+        const uint32_t b = E[min(npad, r * per)], e = E[min(npad, (r + 1) * per)];
+        base[r] = b;
+        mx = max(mx, (unsigned long long)(e - b));
+    }
+    tot[0] = mx;
+}
+// rank r's rows start at r * slot: E[i] -> the row's place in the gathered CSR
+__global__ void k_sh_shift(uint32_t* E, uint32_t npad, uint32_t per, uint32_t slot,
+                           const uint32_t* __restrict__ base) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npad) return;
+    const uint32_t r = i / per;
+    E[i] = E[i] - base[r] + r * slot;
+}
+
+// the CSR's links: in-degrees, the link count, the links whose reverse exists
+__global__ void k_sh_links(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
+                           const uint32_t* __restrict__ adj, uint32_t n, uint32_t* indeg, unsigned long long* sg) {
+    __shared__ unsigned long long sh[2];
+    if (threadIdx.x < 2) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t c = i < n ? cnt[i] : 0;
+    if (c) {
+        const uint32_t* row = adj + off[i];
+        uint32_t m = 0;
+        for (uint32_t k = 0; k < c; k++) {
+            const uint32_t p = row[k];
+            if (p >= n) continue;                     // (never: the pack pass keeps live ids < N)
+            atomicAdd(&indeg[p], 1u);
+            m += sh_has(off, cnt, adj, p, i) ? 1u : 0u;
+        }
+        atomicAdd(&sh[0], (unsigned long long)c);
+        if (m) atomicAdd(&sh[1], (unsigned long long)m);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && sh[threadIdx.x]) atomicAdd(&sg[SG_LINKS + threadIdx.x], sh[threadIdx.x]);
+}
+
+__global__ void k_sh_in(const uint32_t* __restrict__ indeg, const uint8_t* __restrict__ cnt,
+                        const uint8_t* __restrict__ flags, uint32_t n, unsigned long long* sg) {
+    __shared__ unsigned long long sh[SG_ISOL + 1];
+    for (uint32_t j = threadIdx.x; j <= SG_ISOL; j += blockDim.x) sh[j] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (flags[i] & F_UP)) {
+        const uint32_t d = indeg[i];
+        atomicAdd(&sh[hbin(d)], 1ull);
+        atomicMax(&sh[SG_INMAX], (unsigned long long)d);
+        if (!d && !cnt[i]) atomicAdd(&sh[SG_ISOL], 1ull);
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j <= SG_ISOL; j += blockDim.x) {
+        if (!sh[j]) continue;                         // (the link words stay zero here: k_sh_links')
+        if (j == SG_INMAX) atomicMax(&sg[j], sh[j]);
+        else atomicAdd(&sg[j], sh[j]);
+    }
+}
+
+// full strategy: the lowest live id (low: preset to PSIM_NONE), then a wave
+// per node over its member row -- |add & ~remove| and its equality with the
+// lowest live node's; the remove halves are read only once a removal exists
+__global__ void k_sh_low(const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n, uint32_t* low) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (flags[lo + i] & F_UP)) atomicMin(low, i);
+}
+__global__ void __launch_bounds__(BLK) k_sh_full(const uint32_t* __restrict__ fbits, const uint8_t* __restrict__ flags,
+                                                 uint32_t lo, uint32_t n, uint32_t fw, uint32_t tomb,
+                                                 const uint32_t* __restrict__ low, unsigned long long* sf) {
+    const uint32_t i = blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);         // (uniform per wave)
+    if (i >= n || !(flags[lo + i] & F_UP)) return;
+    const uint32_t* row = fbits + (size_t)i * 2 * fw;
+    const uint32_t* ref = fbits + (size_t)*low * 2 * fw;
+    uint32_t c = 0;
+    bool differs = false;
+    for (uint32_t w = lane_id(); w < fw; w += 64) {
+        const uint32_t q = tomb ? row[w] & ~row[fw + w] : row[w];
+        const uint32_t r = tomb ? ref[w] & ~ref[fw + w] : ref[w];
+        c += (uint32_t)__popc(q);
+        differs |= q != r;
+    }
+    c = sh_wave_sum(c);
+    const bool agree = ballot(differs) == 0;
+    if (lane_id() == 0) {
+        atomicAdd(&sf[SF_NUP], 1ull);
+        atomicMin(&sf[SF_MIN], (unsigned long long)c);
+        atomicMax(&sf[SF_MAX], (unsigned long long)c);
+        atomicAdd(&sf[SF_SUM], (unsigned long long)c);
+        if (agree) atomicAdd(&sf[SF_AGREE], 1ull);
+    }
 }
 
 // ------------------------------------------------------------- buffers --
@@ -2141,8 +2401,8 @@ __device__ T block_excl(T v, T* total) {
     return base + x - v;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(BLK) k_scan_tiles(const T* __restrict__ in, uint32_t n, T* __restrict__ sums) {
+template <typename T, typename TI>
+__global__ void __launch_bounds__(BLK) k_scan_tiles(const TI* __restrict__ in, uint32_t n, T* __restrict__ sums) {
     const size_t b0 = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
     T v = 0;
 #pragma unroll
@@ -2184,8 +2444,8 @@ __global__ void __launch_bounds__(BLK) k_scan_sums(T* sums, uint32_t nt) {
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(BLK) k_scan_apply(const T* __restrict__ in, T* __restrict__ out, uint32_t n,
+template <typename T, typename TI>
+__global__ void __launch_bounds__(BLK) k_scan_apply(const TI* __restrict__ in, T* __restrict__ out, uint32_t n,
                                                    const T* __restrict__ sums) {
     const size_t b0 = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
     T x[SCAN_ITEMS], v = 0;
@@ -2203,20 +2463,21 @@ __global__ void __launch_bounds__(BLK) k_scan_apply(const T* __restrict__ in, T*
     }
 }
 
-template <typename T>
-int scan_excl(Shard* s, const T* in, T* out, uint32_t n) {
+// (TI: the input's type where it is narrower than the sums', e.g. byte counts)
+template <typename T, typename TI>
+int scan_excl(Shard* s, const TI* in, T* out, uint32_t n) {
     // (a single-pass decoupled look-back measured 1.5 % slower a step at
     // 2^20, profiles/r03/p25: its device-coherent status loads cost more than
     // the two launches it saves; removed in round 4)
     const uint32_t nt = (uint32_t)(((uint64_t)n + SCAN_TILE - 1) / SCAN_TILE);
     if (nt <= 1) {
-        k_scan_apply<T><<<1, BLK, 0, s->stream>>>(in, out, n, nullptr);
+        k_scan_apply<T, TI><<<1, BLK, 0, s->stream>>>(in, out, n, nullptr);
     } else {
         TRY(s->cub_tmp.ensure((size_t)nt * sizeof(T)));
         T* sums = reinterpret_cast<T*>(s->cub_tmp.p);
-        k_scan_tiles<T><<<nt, BLK, 0, s->stream>>>(in, n, sums);
+        k_scan_tiles<T, TI><<<nt, BLK, 0, s->stream>>>(in, n, sums);
         k_scan_sums<T><<<1, BLK, 0, s->stream>>>(sums, nt);
-        k_scan_apply<T><<<nt, BLK, 0, s->stream>>>(in, out, n, sums);
+        k_scan_apply<T, TI><<<nt, BLK, 0, s->stream>>>(in, out, n, sums);
     }
     HIP_TRY(hipGetLastError());
     return PSIM_OK;
@@ -4196,6 +4457,28 @@ int psim_get_delivery(psim_handle* h, uint32_t first, uint32_t count, uint8_t* h
     return PSIM_OK;
 }
 
+// weakly connected components of the live nodes over the rows k_cc_hook
+// reads: label propagation to a fixed point, then the component count and the
+// largest (comps, largest: zeroed device words; L, size: n words, size zeroed)
+static int cc_run(const uint32_t* off, const uint8_t* rn, const uint32_t* adj, const uint8_t* fl, uint32_t n,
+                  uint32_t* L, uint32_t* size, uint32_t* flag, unsigned long long* comps,
+                  unsigned long long* largest, hipStream_t st) {
+    k_cc_init<<<grid_for(n), BLK, 0, st>>>(fl, n, L);
+    for (int it = 0; it < 4096; it++) {
+        uint32_t changed = 0;
+        HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
+        k_cc_hook<<<grid_for(n), BLK, 0, st>>>(off, rn, adj, fl, n, L, flag);
+        k_cc_jump<<<grid_for(n), BLK, 0, st>>>(n, L);
+        HIP_TRY(hipMemcpyAsync(&changed, flag, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (!changed) break;
+    }
+    k_cc_count<<<grid_for(n), BLK, 0, st>>>(L, n, size, comps);
+    k_cc_max<<<grid_for(n), BLK, 0, st>>>(size, n, largest);
+    HIP_TRY(hipGetLastError());
+    return PSIM_OK;
+}
+
 int psim_get_histograms(psim_handle* h, psim_histograms* out) {
     if (!h || !out) return PSIM_EINVAL;
     if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE) return PSIM_EUNSUPPORTED;
@@ -4264,23 +4547,115 @@ int psim_get_histograms(psim_handle* h, psim_histograms* out) {
         const uint8_t* fl = s0->flags.p;         // replicated: every shard holds all N
         TRY(L.alloc_on(n, st)); TRY(sz.alloc_on(n, st)); TRY(flag.alloc_on(1, st)); TRY(r.alloc_on(3, st));
         k_hist_sym<<<grid_for(n), BLK, 0, st>>>(gan.p, gact.p, fl, n, r.p);
-        k_cc_init<<<grid_for(n), BLK, 0, st>>>(fl, n, L.p);
-        for (int it = 0; it < 4096; it++) {
-            uint32_t changed = 0;
-            HIP_TRY(hipMemsetAsync(flag.p, 0, 4, st));
-            k_cc_hook<<<grid_for(n), BLK, 0, st>>>(gan.p, gact.p, fl, n, L.p, flag.p);
-            k_cc_jump<<<grid_for(n), BLK, 0, st>>>(n, L.p);
-            HIP_TRY(hipMemcpyAsync(&changed, flag.p, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (!changed) break;
-        }
-        k_cc_count<<<grid_for(n), BLK, 0, st>>>(L.p, n, sz.p, r.p + 1);
-        k_cc_max<<<grid_for(n), BLK, 0, st>>>(sz.p, n, r.p + 2);
+        TRY(cc_run(nullptr, gan.p, gact.p, fl, n, L.p, sz.p, flag.p, r.p + 1, r.p + 2, st));
         unsigned long long rv[3];
         HIP_TRY(hipMemcpyAsync(rv, r.p, sizeof rv, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         out->symmetric_links = rv[0]; out->components = rv[1]; out->largest_component = rv[2];
     }
+    return PSIM_OK;
+}
+
+// the full strategy's statistics (one shard by construction: psim_create)
+static int strategy_hist_full(psim_handle* h, psim_strategy_histograms* out) {
+    Shard* s = h->shards[0];
+    hipStream_t st = s->stream;
+    TmpBuf<unsigned long long> sf;
+    TmpBuf<uint32_t> low;
+    TRY(sf.alloc_on(SF_N, st)); TRY(low.alloc_on(1, st));
+    HIP_TRY(hipMemsetAsync(sf.p + SF_MIN, 0xFF, 8, st));
+    HIP_TRY(hipMemsetAsync(low.p, 0xFF, 4, st));
+    k_sh_low<<<grid_for(s->n), BLK, 0, st>>>(s->flags.p, s->lo, s->n, low.p);
+    k_sh_full<<<grid_for((uint64_t)s->n * 64), BLK, 0, st>>>(s->fbits.p, s->flags.p, s->lo, s->n, h->fw,
+                                                           h->tomb ? 1u : 0u, low.p, sf.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long v[SF_N];
+    HIP_TRY(hipMemcpyAsync(v, sf.p, sizeof v, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->n_up = v[SF_NUP];
+    if (v[SF_NUP]) {
+        out->members_min = v[SF_MIN]; out->members_max = v[SF_MAX]; out->members_sum = v[SF_SUM];
+        out->agreeing = v[SF_AGREE];
+    }
+    return PSIM_OK;
+}
+
+int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) {
+    if (!h || !out) return PSIM_EINVAL;
+    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE) return PSIM_EUNSUPPORTED;
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    memset(out, 0, sizeof *out);
+    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
+    if (h->cfg.strategy == PSIM_STRATEGY_FULL) return strategy_hist_full(h, out);
+    Shard* s0 = h->shards[0];
+    hipStream_t st = s0->stream;
+    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
+    const uint32_t N = h->N, per = h->per, v2 = h->cfg.strategy == PSIM_STRATEGY_SCAMP_V2 ? 1u : 0u;
+    const uint32_t npad = per * h->G;            // ids by equal per-shard slots (the pad ids hold no links)
+    const uint32_t W = h->ranked ? (uint32_t)h->world : 1u, rper = h->ranked ? per : npad;
+    auto rows_grid = [](uint32_t n) { return (n + SH_NPB - 1) / SH_NPB; };
+    // temporaries: O(N) bytes and words, and the links
+    TmpBuf<unsigned long long> sl, sg, tot;
+    TmpBuf<uint8_t> cnt;
+    TmpBuf<uint32_t> off, base, adj, indeg, L, sz, flag;
+    TRY(sl.alloc_on(SL_N, st)); TRY(sg.alloc_on(SG_N, st)); TRY(tot.alloc_on(1, st));
+    TRY(cnt.alloc_on((size_t)npad + 1, st)); TRY(off.alloc_on((size_t)npad + 1, st)); TRY(base.alloc_on(W, st));
+    // 1. the row pass: per-node statistics, and the link count of every node
+    for (Shard* s : h->shards)
+        if (s->n)
+            k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, cnt.p, nullptr,
+                                                       nullptr, sl.p);
+    HIP_TRY(hipGetLastError());
+    if (h->ranked) TRY(h->comm->all_gather(cnt.p + (size_t)h->rank * per, cnt.p, per, st));
+    // 2. row offsets: a scan of all counts (entry npad: the total); a rank's
+    // rows are packed from the start of its slot, every slot as long as the
+    // largest rank's links, so the gathered CSR is the same everywhere
+    TRY(scan_excl(s0, cnt.p, off.p, npad + 1));
+    k_sh_rank_tot<<<1, 64, 0, st>>>(off.p, rper, W, npad, base.p, tot.p);
+    unsigned long long slot64 = 0;
+    HIP_TRY(hipMemcpyAsync(&slot64, tot.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (slot64 * W > 0xFFFFFFFFull) return PSIM_ENOMEM;       // (row offsets are 32-bit)
+    const uint32_t slot = (uint32_t)slot64;
+    if (W > 1) k_sh_shift<<<grid_for(npad), BLK, 0, st>>>(off.p, npad, rper, slot, base.p);
+    TRY(adj.alloc_on((size_t)slot * W, st));
+    for (Shard* s : h->shards)
+        if (s->n)
+            k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, cnt.p, off.p,
+                                                       adj.p, sl.p);
+    HIP_TRY(hipGetLastError());
+    if (h->ranked && slot) TRY(h->comm->all_gather(adj.p + (size_t)h->rank * slot, adj.p, (size_t)slot * 4, st));
+    // 3. over the whole CSR (every rank the same): in-degrees, reciprocity,
+    // components; the in_view rows are local and probe it
+    TRY(indeg.alloc_on(N, st)); TRY(L.alloc_on(N, st)); TRY(sz.alloc_on(N, st)); TRY(flag.alloc_on(1, st));
+    k_sh_links<<<grid_for(N), BLK, 0, st>>>(off.p, cnt.p, adj.p, N, indeg.p, sg.p);
+    k_sh_in<<<grid_for(N), BLK, 0, st>>>(indeg.p, cnt.p, fl, N, sg.p);
+    if (v2)
+        for (Shard* s : h->shards)
+            if (s->n)
+                k_sh_inv<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sinv.p, fl, s->lo, s->n, N, off.p, cnt.p,
+                                                          adj.p, sl.p);
+    HIP_TRY(hipGetLastError());
+    TRY(cc_run(off.p, cnt.p, adj.p, fl, N, L.p, sz.p, flag.p, sg.p + SG_COMPS, sg.p + SG_LARGEST, st));
+    if (h->ranked) {                             // the local sums over ranks; the longest view: max
+        TRY(h->comm->all_reduce(sl.p, SL_VMAX, CType::U64, COp::SUM, st));
+        TRY(h->comm->all_reduce(sl.p + SL_VMAX, 1, CType::U64, COp::MAX, st));
+    }
+    unsigned long long lv[SL_N], gv[SG_N];
+    HIP_TRY(hipMemcpyAsync(lv, sl.p, sizeof lv, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(gv, sg.p, sizeof gv, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < PSIM_HIST_BINS; k++) {
+        out->view_fill[k] = lv[SL_VFILL * PSIM_HIST_BINS + k];
+        out->in_fill[k] = lv[SL_IFILL * PSIM_HIST_BINS + k];
+        out->out_degree[k] = lv[SL_OUT * PSIM_HIST_BINS + k];
+        out->in_degree[k] = gv[k];
+    }
+    out->n_up = lv[SL_NUP]; out->view_sum = lv[SL_VSUM]; out->in_sum = lv[SL_ISUM]; out->view_max = lv[SL_VMAX];
+    out->dangling_links = lv[SL_DANG]; out->self_entries = lv[SL_SELF]; out->duplicate_entries = lv[SL_DUP];
+    out->in_view_links = lv[SL_IVL]; out->in_view_confirmed = lv[SL_IVC];
+    out->links = gv[SG_LINKS]; out->mutual_links = gv[SG_MUTUAL]; out->in_degree_max = gv[SG_INMAX];
+    out->isolated = gv[SG_ISOL]; out->components = gv[SG_COMPS]; out->largest_component = gv[SG_LARGEST];
     return PSIM_OK;
 }
 

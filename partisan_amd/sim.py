@@ -358,6 +358,19 @@ class Simulator(_Driver):
         self._check(self._extra["get_exchange_stats"](self._h, C.byref(r), C.byref(b)), "get_exchange_stats")
         return r.value, b.value
 
+    def strategy_histograms(self):
+        """Overlay statistics of a pluggable handle (psim_strategy_histograms)
+        as a dict of ints / arrays; a collective on rank handles."""
+        h = _abi.PsimStrategyHistograms()
+        self._check(self._extra["get_strategy_histograms"](self._h, C.byref(h)), "get_strategy_histograms")
+        out = {}
+        for name, _ in _abi.PsimStrategyHistograms._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(h, name)
+            out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
+        return out
+
     # (k_node_prep: the quiet lazy ticks it counts without running the node)
     KERNELS = ("k_relay", "k_shuf", "k_lite_half", "k_consume", "k_ptl", "k_pt", "k_node_prep")
 
