@@ -2227,10 +2227,13 @@ struct psim_handle {
     int device = 0;
     uint32_t consume_blocks = 1024;     // resident k_consume blocks on the device
     uint32_t pt_blocks = 1024;          // ... and k_pt blocks
-    uint32_t lite_blocks = 1024;        // ... and k_consume_lite (k_lite_half) blocks
+    uint32_t lite_blocks = 1024;        // ... and the lite kernel's blocks
     // the lite list's kernel: k_lite_half, two nodes per wave (psim_lite.hip);
     // PSIM_LITE_WAVE=1 keeps the wave-per-node k_consume_lite (A/B)
     bool lite_half = true;
+    // ... of which k_lite_quarter, four nodes per wave, is the default;
+    // PSIM_LITE_HALF=1 keeps k_lite_half (A/B)
+    bool lite_quarter = true;
     uint32_t ptl_blocks = 1024;         // ... and k_ptl blocks
     uint64_t round = 0;
     // a round failed half-way (psim_step returned an error from inside a
@@ -2614,8 +2617,11 @@ int phase_events_prepare(psim_handle* h, Shard* s, const RoundCtl& ctl, RoundArg
         s->rgrid = hv ? std::min<uint32_t>(grid_for(n), RELAY_MAX_BLOCKS) : 0;
         s->tgrid = hv && h->cfg.plumtree ? std::min<uint32_t>(grid_for(n), h->pt_blocks) : 0;
         s->sgrid = hv ? std::min<uint32_t>(grid_for(n), SHUF_MAX_BLOCKS) : 0;
-        // (k_lite_half: two nodes per wave)
-        const uint32_t lnodes = h->lite_half ? psim::lite_half_block() * 2 : psim::lite_block();
+        // (k_lite_quarter: four nodes per wave, a row of 16 lanes per local
+        // node -- at 2^20 nodes the cap lite_blocks decides, psim_create;
+        // k_lite_half as tuned in round 4)
+        const uint32_t lnodes = h->lite_quarter ? psim::lite_quarter_block() / 16
+                              : h->lite_half ? psim::lite_half_block() * 2 : psim::lite_block();
         s->lgrid = hv ? std::min<uint32_t>((uint32_t)((n + lnodes - 1) / lnodes), h->lite_blocks) : 0;
         const uint32_t qnodes = PTL_BLOCK;
         s->qgrid = hv && h->cfg.plumtree ? std::min<uint32_t>((uint32_t)((n + qnodes - 1) / qnodes), h->ptl_blocks) : 0;
@@ -2699,7 +2705,8 @@ args:
 }
 
 void launch_lite(psim_handle* h, Shard* s, const RoundArgs& a, hipStream_t st) {
-    if (h->lite_half) k_lite_half<<<s->lgrid, psim::lite_half_block(), 0, st>>>(a);
+    if (h->lite_quarter) k_lite_quarter<<<s->lgrid, psim::lite_quarter_block(), 0, st>>>(a);
+    else if (h->lite_half) k_lite_half<<<s->lgrid, psim::lite_half_block(), 0, st>>>(a);
     else k_consume_lite<<<s->lgrid, psim::lite_block(), 0, st>>>(a);
 }
 
@@ -3871,13 +3878,22 @@ int psim_create(const psim_config* cfg, psim_handle** out) {
     };
     h->consume_blocks = grid("PSIM_CONSUME_GRID", psim::consume_grid(), psim::consume_grid());
     h->pt_blocks = grid("PSIM_PT_GRID", psim::pt_grid(), psim::pt_grid());
-    // k_consume_lite: four times the resident blocks -- the dispatcher hands
-    // freed slots new blocks, which evens out the waves' uneven node mixes (the
-    // resident grid left 4.1 of 6 waves/SIMD busy on average; 300 -> 272 us a
-    // round on the survey line, profiles/r03/p10)
+    // the lite list's kernel: k_lite_quarter (four nodes per wave);
+    // PSIM_LITE_HALF=1 keeps k_lite_half (two), PSIM_LITE_WAVE=1 the
+    // wave-per-node k_consume_lite.  The cap is four times the kernel's
+    // resident blocks -- the dispatcher hands freed slots new blocks, which
+    // evens out the waves' uneven node mixes (k_consume_lite: the resident
+    // grid left 4.1 of 6 waves/SIMD busy on average; 300 -> 272 us a round on
+    // the survey line, profiles/r03/p10; k_lite_quarter: x1 0.544, x2 0.540,
+    // x4 0.539, x8 0.545, x16 0.551 ms a step, profiles/lite_quarter/ab_log.txt).
+    // At 2^20 nodes that is 4096 blocks of k_lite_quarter (phase_prepare's
+    // one row per local node would allow 65536); k_lite_half's grid there is
+    // the 2048 blocks phase_prepare allows it
     h->lite_half = getenv("PSIM_LITE_WAVE") == nullptr;
-    h->lite_blocks = h->lite_half ? grid("PSIM_LITE_GRID", psim::lite_half_grid(), 4 * psim::lite_half_grid())
-                                  : grid("PSIM_LITE_GRID", psim::lite_grid(), 4 * psim::lite_grid());
+    h->lite_quarter = h->lite_half && getenv("PSIM_LITE_HALF") == nullptr;
+    h->lite_blocks = h->lite_quarter ? grid("PSIM_LITE_GRID", psim::lite_quarter_grid(), 4 * psim::lite_quarter_grid())
+                   : h->lite_half    ? grid("PSIM_LITE_GRID", psim::lite_half_grid(), 4 * psim::lite_half_grid())
+                                     : grid("PSIM_LITE_GRID", psim::lite_grid(), 4 * psim::lite_grid());
     // k_ptl (a lane per node; round 4's four-nodes-per-wave k_ptq was
     // parity-exact but slower -- 0.602 against 0.584 ms a phase at 2^20, 79.3
     // against 68.1 ms at 2^26, profiles/r04/pq2: a row per node runs each

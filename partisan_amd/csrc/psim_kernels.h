@@ -163,13 +163,17 @@ __global__ void k_consume_lite(RoundArgs args);
 __global__ void k_lite_half(RoundArgs args);
 uint32_t lite_half_grid();
 uint32_t lite_half_block();
+// the same with four nodes per wave, one per 16-lane DPP row (psim_lite.hip)
+__global__ void k_lite_quarter(RoundArgs args);
+uint32_t lite_quarter_grid();
+uint32_t lite_quarter_block();
 // lane-per-node Plumtree phases (psim_consume.hip); hands k_pt what does not fit
 __global__ void k_ptl(RoundArgs args);
 // the Plumtree phase of the nodes k_relay listed (psim_consume.hip)
 __global__ void k_pt(RoundArgs args);
 // diagnostic builds (-DPSIM_STAMPS): per-phase cycle sums of k_consume, reset on read
 int debug_stamps(unsigned long long* out);
-int debug_stamps_half(unsigned long long* out);   // k_lite_half's 32 (psim_lite.hip)
+int debug_stamps_half(unsigned long long* out);   // the lite kernel's 32 (psim_lite.hip)
 // resident-block count of k_consume on the current device
 uint32_t consume_grid();
 uint32_t lite_grid();
@@ -210,9 +214,9 @@ __device__ __forceinline__ uint4 ptl_desc(Args& a, uint32_t n0, uint32_t i) {
 // entry i of the lite list, in four bins k_relay fills: nodes with a SHUFFLE
 // terminal (a sublist of the passive view, a reply and a merge) and nothing
 // else, nodes with only replies' merges, then the same two with more work
-// beside (SHUFFLE relays in the inbox, a due shuffle start) -- k_lite_half
-// pairs adjacent entries in a wave's two halves, so most pairs run the same
-// handlers and neither half waits on the other's extra work
+// beside (SHUFFLE relays in the inbox, a due shuffle start) -- k_lite_quarter
+// puts four adjacent entries in a wave's rows (k_lite_half two in its halves),
+// so most run the same handlers and none waits on another's extra work
 template <class Args>
 __device__ __forceinline__ uint32_t lite_at(Args& a, const uint32_t (&c)[4], uint32_t i) {
     const uint32_t n = a.n_local;

@@ -22,7 +22,7 @@ import json
 import os
 import sys
 
-KERNELS = ("k_relay(", "k_shuf(", "k_consume_lite(", "k_lite_half(", "k_term(", "k_consume(", "k_ptl(", "k_ptq(",
+KERNELS = ("k_relay(", "k_shuf(", "k_consume_lite(", "k_lite_half(", "k_lite_quarter(", "k_term(", "k_consume(", "k_ptl(", "k_ptq(",
            "k_pt(", "k_consume_pl(")
 
 
@@ -48,6 +48,12 @@ def main():
     by = {}
     fetch = per_round(sys.argv[2], steps, tail, by)
     write = per_round(sys.argv[3], steps, tail, by)
+    # bench.py's per-kernel counts keep "k_lite_half" as the lite kernel's slot
+    # (sim.py KERNELS), whichever lite kernel ran: the excess under that name
+    # is k_lite_quarter's counted bytes when that is the kernel in the trace
+    counted = dict(by)
+    if "k_lite_quarter" in by and "k_lite_half" not in by:
+        counted["k_lite_half"] = by["k_lite_quarter"]
     rec = {"key": bench["pmc_key"],
            "traffic_per_launch": fetch + write,
            "traffic_upper_per_launch": 2 * fetch + write,
@@ -57,7 +63,7 @@ def main():
            # each kernel's algorithmic bytes per round (bench.py --kernel-counts:
            # its own nodes processed, deliveries, emissions) and counted / algorithmic
            "per_kernel_alg": bench.get("per_kernel_alg"),
-           "per_kernel_excess": ({k: by[k] / a for k, a in bench["per_kernel_alg"].items() if a and k in by}
+           "per_kernel_excess": ({k: counted[k] / a for k, a in bench["per_kernel_alg"].items() if a and k in counted}
                                  if bench.get("per_kernel_alg") else None),
            "source": "FETCH_SIZE + WRITE_SIZE per timed round of the node-round kernels, separate "
                      "rocprofv3 --pmc passes of this command (profiles/run_pmc.sh); FETCH_SIZE uncorrected: "

@@ -30,7 +30,7 @@ for i, n in enumerate(PT):
     NAMES[16 + i] = "pt:" + n
 HALF = {8: "loop / wait for the node's loads", 0: "begin + connection cache", 6: "inbox record parse",
         1: "SHUFFLE relay", 2: "terminal: sublist", 3: "terminal: reply send", 4: "merge_exchange",
-        5: "shuffle start", 7: "writeback + flush", 9: "body's end (the other half's work)"}
+        5: "shuffle start", 7: "writeback + flush", 9: "body's end (the other rows' / half's work)"}
 PTL = {0: "list entry, rows, records, preconditions", 1: "k_pt list append", 2: "active row + connection mask",
        3: "sets / table loads", 4: "update_peers (every message)", 5: "BROADCAST first: eager push + lazy adds",
        9: "IGNORED_IHAVE ack", 10: "answer send",
@@ -96,7 +96,8 @@ def main():
         print("k_ptl (wave time by phase; a divergent handler's branches each charged their own):")
         table(v[48:64], PTL, a.steps)
     if v[64:].any():
-        print("k_lite_half (each half's phases; both halves summed):")
+        print("the lite kernel -- k_lite_quarter, or k_lite_half under PSIM_LITE_HALF=1 (each row's / half's "
+              "phases; slots 0-15: rows 0 and 2 / half 0, slots 16-31: rows 1 and 3 / half 1; summed):")
         table(v[64:80] + v[80:96], HALF, a.steps)
 
 
