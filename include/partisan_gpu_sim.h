@@ -550,7 +550,8 @@ int psim_wire_decode(const uint8_t *buf, size_t len, const psim_wire_names *name
                      size_t *used);
 
 /* Diagnostic: per node-round kernel of the last round (k_relay, k_shuf,
- * k_lite_half, k_consume, k_ptl, k_pt; this process's first shard), 4 words
+ * the lite kernel, k_consume, k_ptl, k_pt; this process's first shard; the
+ * lite kernel is k_lite_quarter, k_lite_half or k_consume_lite), 4 words
  * each: nodes processed, records delivered, records emitted, 0 -- the
  * kernel's share of the algorithmic bytes (bench.py --kernel-counts,
  * profiles/pmc_record.py).  With cap >= 28 a seventh entry, k_node_prep:

@@ -2423,7 +2423,7 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
                 }
         }
         if (P < na && lite && !heavy) {
-            // the lite node's connection bits (k_lite_half's connect_ok)
+            // the lite node's connection bits (psim_lite.hip connect_ok)
             uint32_t cm = 0;
 #pragma unroll
             for (int j = 0; j < 8; j++)
@@ -3343,20 +3343,13 @@ __global__ void PTL_BOUNDS k_ptl(RoundArgs) {
     }
 }
 
-// one wave-slot per resident wave: the grid strides over the active list
-// with no second generation of waves (a partial generation is a tail)
-static uint32_t resident_grid(const void* k, int block = WAVES_PER_BLOCK * 64) {
-    int dev = 0, nb = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, block, 0) != hipSuccess || nb <= 0)
-        return 1024;
-    return (uint32_t)nb * (uint32_t)p.multiProcessorCount;
+uint32_t consume_grid() { return resident_grid((const void*)k_consume, WAVES_PER_BLOCK * 64); }
+// (a block of k_consume_lite per block's worth of local nodes, capped)
+LiteKernel lite_kernel_wave() {
+    constexpr uint32_t b = 64 * LITE_WPB;
+    return {k_consume_lite, b, b, resident_grid((const void*)k_consume_lite, b), true};
 }
-uint32_t consume_grid() { return resident_grid((const void*)k_consume); }
-uint32_t lite_grid() { return resident_grid((const void*)k_consume_lite, 64 * LITE_WPB); }
-uint32_t lite_block() { return 64 * LITE_WPB; }
-uint32_t pt_grid() { return resident_grid((const void*)k_pt); }
+uint32_t pt_grid() { return resident_grid((const void*)k_pt, WAVES_PER_BLOCK * 64); }
 uint32_t ptl_grid() { return resident_grid((const void*)k_ptl, PTL_BLK); }
 
 #ifdef PSIM_STAMPS
@@ -3368,7 +3361,7 @@ int debug_stamps(unsigned long long* out) {
     unsigned long long z[32] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof z) != hipSuccess) return -1;
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamps_lite), z, sizeof z) != hipSuccess) return -1;
-    // k_lite_half's, when it ran (psim_lite.hip): 96 entries
+    // k_lite_quarter's / k_lite_half's, when one ran (psim_lite.hip): 96 entries
     if (debug_stamps_half(out + 64) != 32) return -1;
     return 96;
 }

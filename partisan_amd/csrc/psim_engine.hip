@@ -2227,13 +2227,11 @@ struct psim_handle {
     int device = 0;
     uint32_t consume_blocks = 1024;     // resident k_consume blocks on the device
     uint32_t pt_blocks = 1024;          // ... and k_pt blocks
-    uint32_t lite_blocks = 1024;        // ... and the lite kernel's blocks
-    // the lite list's kernel: k_lite_half, two nodes per wave (psim_lite.hip);
-    // PSIM_LITE_WAVE=1 keeps the wave-per-node k_consume_lite (A/B)
-    bool lite_half = true;
-    // ... of which k_lite_quarter, four nodes per wave, is the default;
-    // PSIM_LITE_HALF=1 keeps k_lite_half (A/B)
-    bool lite_quarter = true;
+    uint32_t lite_blocks = 1024;        // the cap of the lite kernel's grid
+    // the lite list's kernel, chosen in psim_create: k_lite_quarter, four
+    // nodes per wave (psim_lite.hip); PSIM_LITE_HALF=1 keeps k_lite_half
+    // (two), PSIM_LITE_WAVE=1 the wave-per-node k_consume_lite (A/B)
+    psim::LiteKernel lite = {};
     uint32_t ptl_blocks = 1024;         // ... and k_ptl blocks
     uint64_t round = 0;
     // a round failed half-way (psim_step returned an error from inside a
@@ -2617,11 +2615,9 @@ int phase_events_prepare(psim_handle* h, Shard* s, const RoundCtl& ctl, RoundArg
         s->rgrid = hv ? std::min<uint32_t>(grid_for(n), RELAY_MAX_BLOCKS) : 0;
         s->tgrid = hv && h->cfg.plumtree ? std::min<uint32_t>(grid_for(n), h->pt_blocks) : 0;
         s->sgrid = hv ? std::min<uint32_t>(grid_for(n), SHUF_MAX_BLOCKS) : 0;
-        // (k_lite_quarter: four nodes per wave, a row of 16 lanes per local
-        // node -- at 2^20 nodes the cap lite_blocks decides, psim_create;
-        // k_lite_half as tuned in round 4)
-        const uint32_t lnodes = h->lite_quarter ? psim::lite_quarter_block() / 16
-                              : h->lite_half ? psim::lite_half_block() * 2 : psim::lite_block();
+        // (k_lite_quarter: a row of 16 lanes per local node -- at 2^20 nodes
+        // the cap lite_blocks decides, psim_create)
+        const uint32_t lnodes = h->lite.grid_nodes;
         s->lgrid = hv ? std::min<uint32_t>((uint32_t)((n + lnodes - 1) / lnodes), h->lite_blocks) : 0;
         const uint32_t qnodes = PTL_BLOCK;
         s->qgrid = hv && h->cfg.plumtree ? std::min<uint32_t>((uint32_t)((n + qnodes - 1) / qnodes), h->ptl_blocks) : 0;
@@ -2705,9 +2701,7 @@ args:
 }
 
 void launch_lite(psim_handle* h, Shard* s, const RoundArgs& a, hipStream_t st) {
-    if (h->lite_quarter) k_lite_quarter<<<s->lgrid, psim::lite_quarter_block(), 0, st>>>(a);
-    else if (h->lite_half) k_lite_half<<<s->lgrid, psim::lite_half_block(), 0, st>>>(a);
-    else k_consume_lite<<<s->lgrid, psim::lite_block(), 0, st>>>(a);
+    h->lite.kernel<<<s->lgrid, h->lite.block, 0, st>>>(a);
 }
 
 int phase_consume(psim_handle* h, Shard* s, RoundArgs& a) {
@@ -2741,7 +2735,7 @@ int phase_consume(psim_handle* h, Shard* s, RoundArgs& a) {
         RoundArgs b = a;
         b.desc = s->desc_slow.p;
         b.n_alist = s->n_slow.p;
-        // k_shuf, k_consume_lite and k_consume take k_relay's disjoint lists
+        // k_shuf, the lite kernel and k_consume take k_relay's disjoint lists
         // and write only their own nodes' rows, records and stats rows: they
         // run side by side (k_shuf and k_consume, latency-bound at ~1 and
         // ~0.5 waves/SIMD, fill k_consume_lite's tail), then join before the
@@ -2751,14 +2745,15 @@ int phase_consume(psim_handle* h, Shard* s, RoundArgs& a) {
         // 2^26: 15 ms of wave work a round) and side by side with
         // k_consume_lite the two took longer than one after the other
         // (node-round phase 61.0 -> 68.3 ms, profiles/r03/p36)
-        // Since round 4 (k_lite_half) the kernels run one after another by
-        // default: side by side with k_lite_half's 128-VGPR waves the phase
-        // took 0.61 ms against 0.58 serially, and the step 0.84 against 0.77
-        // (profiles/r04/p8); PSIM_CONCURRENT_PHASE=1 restores the side streams
-        // outside crash rounds (and, with the wave kernel, PSIM_LITE_WAVE=1)
+        // With k_lite_quarter or k_lite_half the kernels run one after
+        // another by default: side by side with k_lite_half's 128-VGPR waves
+        // the phase took 0.61 ms against 0.58 serially, and the step 0.84
+        // against 0.77 (profiles/r04/p8); PSIM_CONCURRENT_PHASE=1 restores
+        // the side streams outside crash rounds, and the wave kernel
+        // (PSIM_LITE_WAVE=1) keeps them (LiteKernel::side_by_side)
         static const bool conc_env = getenv("PSIM_CONCURRENT_PHASE") != nullptr;
         static const bool serial_env = getenv("PSIM_SERIAL_PHASE") != nullptr;
-        const bool serial = serial_env || a.crash_round || !(conc_env || !h->lite_half);
+        const bool serial = serial_env || a.crash_round || !(conc_env || h->lite.side_by_side);
         if (serial) {
             k_shuf<<<s->sgrid, BLK, 0, s->stream>>>(a);
             launch_lite(h, s, a, s->stream);
@@ -3888,12 +3883,10 @@ int psim_create(const psim_config* cfg, psim_handle** out) {
     // x4 0.539, x8 0.545, x16 0.551 ms a step, profiles/lite_quarter/ab_log.txt).
     // At 2^20 nodes that is 4096 blocks of k_lite_quarter (phase_prepare's
     // one row per local node would allow 65536); k_lite_half's grid there is
-    // the 2048 blocks phase_prepare allows it
-    h->lite_half = getenv("PSIM_LITE_WAVE") == nullptr;
-    h->lite_quarter = h->lite_half && getenv("PSIM_LITE_HALF") == nullptr;
-    h->lite_blocks = h->lite_quarter ? grid("PSIM_LITE_GRID", psim::lite_quarter_grid(), 4 * psim::lite_quarter_grid())
-                   : h->lite_half    ? grid("PSIM_LITE_GRID", psim::lite_half_grid(), 4 * psim::lite_half_grid())
-                                     : grid("PSIM_LITE_GRID", psim::lite_grid(), 4 * psim::lite_grid());
+    // the 2048 blocks phase_prepare allows it (LiteKernel::grid_nodes)
+    h->lite = getenv("PSIM_LITE_WAVE") ? psim::lite_kernel_wave()
+                                       : psim::lite_kernel_groups(getenv("PSIM_LITE_HALF") != nullptr);
+    h->lite_blocks = grid("PSIM_LITE_GRID", h->lite.resident, 4 * h->lite.resident);
     // k_ptl (a lane per node; round 4's four-nodes-per-wave k_ptq was
     // parity-exact but slower -- 0.602 against 0.584 ms a phase at 2^20, 79.3
     // against 68.1 ms at 2^26, profiles/r04/pq2: a row per node runs each
@@ -4866,7 +4859,7 @@ int psim_kernel_times(psim_handle* h, const char** names, double* ms, uint64_t* 
 
 // diagnostic: per node-round kernel of the last round (shard 0's blocks; the
 // stats rows every block leaves, before the route sums them), in the order
-// k_relay, k_shuf, k_lite_half / k_consume_lite, k_consume, k_ptl,
+// k_relay, k_shuf, the lite kernel (psim_handle::lite), k_consume, k_ptl,
 // k_pt: out[4 k] nodes processed (stats nodes_processed), out[4 k + 1]
 // records delivered, out[4 k + 2] records emitted, out[4 k + 3] 0; with cap
 // >= 28 then k_node_prep's quiet lazy ticks (nodes processed without a
@@ -4899,7 +4892,7 @@ int psim_debug_kernel_counts(psim_handle* h, uint64_t* out, int cap) {
 }
 
 // diagnostic: per-phase s_memtime sums of k_consume / k_pt, k_consume_lite and
-// k_lite_half (96 entries; 0 returned unless built with -DPSIM_STAMPS)
+// k_lite_quarter / k_lite_half (96 entries; 0 returned unless built with -DPSIM_STAMPS)
 int psim_debug_stamps(unsigned long long* out, int cap) {
     if (!out || cap < 96) return PSIM_EINVAL;
     return psim::debug_stamps(out);

@@ -43,11 +43,11 @@ struct RoundArgs {
     // change only there), so a connection test of a peer reads one byte pair
     // instead of a flag byte and a partition byte on two random lines (k_ptl:
     // eight members a node, 63 GB a round at 2^26 before; k_relay, k_shuf,
-    // k_lite_half likewise; HyParView / X-BOT handles only)
+    // the lite kernel likewise; HyParView / X-BOT handles only)
     upart_t* upart;
     // per local node of k_relay's lite list: bit j = active member j is up in
     // this node's partition group (k_relay reads the pairs for it before its
-    // list appends; k_lite_half reads the byte with the node's rows, a node
+    // list appends; the lite kernel reads the byte with the node's rows, a node
     // ahead, instead of eight dependent pair loads as the node starts)
     uint8_t* lite_cm;
     // this round's crashed ids, one bit per CRASH_GRAIN ids (replicated,
@@ -89,10 +89,10 @@ struct RoundArgs {
     uint4* desc_shuf;           // ... and the nodes whose HyParView phase ends in a shuffle start, for k_shuf
     uint32_t* n_shuf;
     uint64_t* stat_shuf;        // k_shuf's per-block stats rows
-    uint4* desc_lite;           // ... and the nodes with SHUFFLE terminals / replies, for k_lite_half:
+    uint4* desc_lite;           // ... and the nodes with SHUFFLE terminals / replies, for the lite kernel:
     uint32_t* n_lite;           // 2 n_local slots, four bins (lite_at): [0] and [1] from the first
                                 // half's front and back, [2] and [3] from the second's
-    uint64_t* stat_lite;        // k_consume_lite's per-block stats rows
+    uint64_t* stat_lite;        // the lite kernel's per-block stats rows
     uint4* desc_ptl;            // ... and the nodes with Plumtree work and no origin, for k_ptl:
     uint32_t* n_ptl;            // [0] from the front, those with a BROADCAST in their inbox, [1] from
                                 // the back (desc_ptl[n_local - 1 - i]), the others (ptl_desc)
@@ -157,16 +157,23 @@ __global__ void k_relay(RoundArgs args);
 __global__ void k_consume_pl(RoundArgs args);
 // lane-per-node shuffle starts of the nodes k_relay listed (psim_consume.hip)
 __global__ void k_shuf(RoundArgs args);
-// wave-per-node SHUFFLE terminals, replies and their merges (psim_consume.hip)
+// The lite kernel: SHUFFLE terminals, replies and their merges of k_relay's
+// lite list.  Four nodes per wave, one per 16-lane DPP row (k_lite_quarter,
+// psim_lite.hip: the default); two, one per 32-lane half (k_lite_half,
+// PSIM_LITE_HALF=1); or a wave per node (k_consume_lite, psim_consume.hip,
+// PSIM_LITE_WAVE=1).  psim_create picks one and keeps its descriptor.
 __global__ void k_consume_lite(RoundArgs args);
-// the same with two nodes per wave, one per 32-lane half (psim_lite.hip)
 __global__ void k_lite_half(RoundArgs args);
-uint32_t lite_half_grid();
-uint32_t lite_half_block();
-// the same with four nodes per wave, one per 16-lane DPP row (psim_lite.hip)
 __global__ void k_lite_quarter(RoundArgs args);
-uint32_t lite_quarter_grid();
-uint32_t lite_quarter_block();
+struct LiteKernel {
+    void (*kernel)(RoundArgs);
+    uint32_t block;             // threads per block
+    uint32_t grid_nodes;        // the grid is a block per grid_nodes local nodes, capped (phase_prepare)
+    uint32_t resident;          // resident blocks on the current device
+    bool side_by_side;          // runs beside k_shuf and k_consume by default (phase_consume)
+};
+LiteKernel lite_kernel_groups(bool half);   // k_lite_quarter / k_lite_half (psim_lite.hip)
+LiteKernel lite_kernel_wave();              // k_consume_lite (psim_consume.hip)
 // lane-per-node Plumtree phases (psim_consume.hip); hands k_pt what does not fit
 __global__ void k_ptl(RoundArgs args);
 // the Plumtree phase of the nodes k_relay listed (psim_consume.hip)
@@ -176,8 +183,6 @@ int debug_stamps(unsigned long long* out);
 int debug_stamps_half(unsigned long long* out);   // the lite kernel's 32 (psim_lite.hip)
 // resident-block count of k_consume on the current device
 uint32_t consume_grid();
-uint32_t lite_grid();
-uint32_t lite_block();
 uint32_t pt_grid();
 uint32_t ptl_grid();
 
@@ -266,6 +271,17 @@ constexpr uint32_t layout_sig() {
 uint32_t layout_sig_consume();
 uint32_t layout_sig_lite();
 uint32_t layout_sig_strategy();
+
+// one wave-slot per resident wave: the grid strides over the kernel's list
+// with no second generation of waves (a partial generation is a tail)
+inline uint32_t resident_grid(const void* kernel, uint32_t block) {
+    int dev = 0, nb = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, (int)block, 0) != hipSuccess || nb <= 0)
+        return 1024;
+    return (uint32_t)nb * (uint32_t)p.multiProcessorCount;
+}
 
 __device__ __forceinline__ KArgs& kargs() {
     KArgs* p = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();

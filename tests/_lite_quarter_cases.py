@@ -9,8 +9,9 @@ F   full passive views at the slot boundaries: max_passive_size 1 (slot 0 of
     past the half cap), 30 with one-element shuffles
 F16 a 16-entry view with four-element passive samples
 F30 the defaults: 30 entries, every merge of a full view evicts
-D   deep inboxes: SHUFFLE / SHUFFLE_REPLY records past the first 16 of a
-    node's inbox (the kernel reads the inbox 16 records at a time)
+D   deep inboxes: SHUFFLE / SHUFFLE_REPLY records past the first 16 and the
+    first 32 of a node's inbox (k_lite_quarter reads the inbox 16 records at
+    a time, k_lite_half 32)
 """
 import numpy as np
 
@@ -44,7 +45,8 @@ def full_share(sim, name):
 # D: every node shuffles every round with a long walk, and from round
 # D_BCAST_FROM on four roots broadcast every round
 # (on the oracle: a largest inbox of 141 records, 260 k SHUFFLE /
-# SHUFFLE_REPLY records at position >= 16, no overflow, in under a second)
+# SHUFFLE_REPLY records at position >= 16, 153 k at >= 32, no overflow, in
+# under a second)
 D_N, D_SEED, D_ROUNDS, D_BCAST_FROM = 1024, 3, 60, 30
 D_ROOTS = (0, 256, 512, 768)
 
@@ -66,9 +68,9 @@ def run_d(make, each_round=None):
     return sim, st
 
 
-def inbox_depths(inbox):
-    """(largest inbox, SHUFFLE / SHUFFLE_REPLY records at position >= 16 of
-    their node's inbox) of an Oracle.inbox() array"""
+def inbox_depths(inbox, position=16):
+    """(largest inbox, SHUFFLE / SHUFFLE_REPLY records at `position` or later
+    in their node's inbox) of an Oracle.inbox() array"""
     if len(inbox) == 0:
         return 0, 0
     dst = inbox[:, 0]
@@ -78,5 +80,5 @@ def inbox_depths(inbox):
     sizes = np.diff(np.r_[start, len(d)])
     pos = np.arange(len(d)) - np.repeat(start, sizes)
     typ = inbox[order, 3] & 0xFF
-    deep = (pos >= 16) & ((typ == MSG_SHUFFLE) | (typ == MSG_SHUFFLE_REPLY))
+    deep = (pos >= position) & ((typ == MSG_SHUFFLE) | (typ == MSG_SHUFFLE_REPLY))
     return int(sizes.max()), int(deep.sum())

@@ -5,7 +5,10 @@ tests/_lite_quarter_cases.py: full passive views at the slot boundaries
 the merge, and inboxes deeper than the 16 records a row reads at a time.
 Every test also checks that the lite kernel did run nodes in a late round,
 so none can pass by the nodes having gone to k_consume.  The two-nodes-a-wave
-k_lite_half stays reachable (PSIM_LITE_HALF=1) and keeps parity."""
+k_lite_half (PSIM_LITE_HALF=1) runs the same handlers with a 32-lane group:
+the same scenarios in a child process each (the knob is read once per
+process) -- they fill its one-entry-a-lane passive view to each boundary, and
+D pushes the inbox past the 32 records a half reads at a time."""
 import os
 import subprocess
 import sys
@@ -50,6 +53,18 @@ def test_deep_inboxes():
     gs, gst = Q.run_d(gpu)
     os_, ost = Q.run_d(Oracle)
     check(gs, gst, os_, ost)
+
+
+HALF_CASES = ["F-m1", "F-m15", "F-m17", "F-m30-k1", "F16", "F30", "F30+buckets", "D"]
+
+
+@pytest.mark.parametrize("name", HALF_CASES)
+def test_half_kernel_scenarios(name):
+    env = dict(os.environ, PSIM_LITE_HALF="1")
+    r = subprocess.run([sys.executable, "-u", os.path.join(HERE, "_lite_case_run.py"), name], env=env,
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "identical" in r.stdout
 
 
 def test_half_kernel_keeps_parity():

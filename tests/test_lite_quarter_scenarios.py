@@ -1,5 +1,6 @@
 """The scenarios of tests/_lite_quarter_cases.py on the oracle alone: each
-still reaches what the GPU tests of k_lite_quarter need it to reach, so that
+still reaches what the GPU tests of k_lite_quarter and k_lite_half need it to
+reach, so that
 a later change of defaults cannot empty those tests."""
 import pytest
 
@@ -17,14 +18,17 @@ def test_full_views_reached(name):
 
 
 def test_deep_inboxes_reached():
-    seen = {"largest": 0, "deep": 0}
+    seen = {"largest": 0, "deep": 0, "deep32": 0}
 
     def each_round(sim, r):
         largest, deep = Q.inbox_depths(sim.inbox())
         seen["largest"] = max(seen["largest"], largest)
         seen["deep"] += deep
+        seen["deep32"] += Q.inbox_depths(sim.inbox(), 32)[1]    # (the half kernel's chunk)
     sim, st = Q.run_d(Oracle, each_round)
     print("largest inbox", seen["largest"], "SHUFFLE / SHUFFLE_REPLY records at position >= 16", seen["deep"])
+    print("... at position >= 32", seen["deep32"])
     assert seen["deep"] >= 1000
+    assert seen["deep32"] >= 1000
     assert seen["largest"] > 32
     assert int(st["overflow"].sum()) == 0
