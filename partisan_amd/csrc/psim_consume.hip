@@ -22,6 +22,7 @@
 //   pt = src/partisan_plumtree_broadcast.erl
 #include "psim_device.h"
 #include "psim_kernels.h"
+#include "psim_lite.h"   // the quarter body of k_hv_phase (below)
 #include "psim_wave.h"
 
 namespace psim {
@@ -1306,9 +1307,13 @@ struct NodeX {
                                    // 40-47), their flags | part << 8
 };
 
+// (SLOW: k_relay's list for k_consume read from where k_relay left it,
+// desc_slow -- k_hv_phase's arguments are the round's, not k_consume's copy
+// with the list in desc / n_alist)
+template <bool SLOW = false>
 DEV uint32_t load_desc(KArgs& a, uint32_t k) {
     uint32_t l = lane_id();
-    return reinterpret_cast<const uint32_t*>(a.desc + k)[l & 3];
+    return reinterpret_cast<const uint32_t*>((SLOW ? a.desc_slow : a.desc) + k)[l & 3];
 }
 
 template <bool CONN = true>
@@ -1683,7 +1688,10 @@ DEV void writeback(Wv& w) {
 
 // one HyParView-phase wave per node of the list (k_relay leaves here every
 // node whose HyParView work is more than one SHUFFLE relay)
-__global__ void __launch_bounds__(256, PSIM_WAVES_PER_SIMD) k_consume(RoundArgs args) {
+// Block `bid` of `nblk`: the launch's own index and grid in k_consume, the
+// consume range's in k_hv_phase (SLOW: the list as k_relay's arguments name it).
+template <bool SLOW>
+DEV void consume_blocks(const RoundArgs& args, const uint32_t bid, const uint32_t nblk) {
     if (*kargs().ctl) return;                         // an aborted batch (run_batch)
     __shared__ uint64_t sst[NST];
     __shared__ uint32_t scratch[WAVES_PER_BLOCK][64];
@@ -1694,8 +1702,8 @@ __global__ void __launch_bounds__(256, PSIM_WAVES_PER_SIMD) k_consume(RoundArgs 
     __syncthreads();
 
     const uint32_t wid = threadIdx.x >> 6;
-    const uint32_t gw = uni(blockIdx.x * WAVES_PER_BLOCK + wid);
-    const uint32_t nw = gridDim.x * WAVES_PER_BLOCK;
+    const uint32_t gw = uni(bid * WAVES_PER_BLOCK + wid);
+    const uint32_t nw = nblk * WAVES_PER_BLOCK;
     Wv w;
     w.a = &args;
     w.lds = scratch[wid];
@@ -1714,7 +1722,7 @@ __global__ void __launch_bounds__(256, PSIM_WAVES_PER_SIMD) k_consume(RoundArgs 
     w.SC = 0;
     w.digest = 0;
     w.KM = magic_lanes();
-    const uint32_t na = *kargs().n_alist;
+    const uint32_t na = *(SLOW ? kargs().n_slow : kargs().n_alist);
     if (gw < na) {
         // Pipeline over this wave's nodes i, i + nw, ...: while node i is
         // processed, the rows of node i + nw are in flight; after its body the
@@ -1722,10 +1730,10 @@ __global__ void __launch_bounds__(256, PSIM_WAVES_PER_SIMD) k_consume(RoundArgs 
         // the rows of node i + 2nw.  Every node issues the same loads and
         // stores, so each wait is for exactly the stage it needs.
         const uint32_t last = na - 1;
-        NodeIn x = load_node(kargs(), load_desc(kargs(), gw));
+        NodeIn x = load_node(kargs(), load_desc<SLOW>(kargs(), gw));
         NodeX y = load_x(kargs(), x);
-        NodeIn xn = load_node(kargs(), load_desc(kargs(), min(gw + nw, last)));
-        uint32_t d = load_desc(kargs(), min(gw + 2 * nw, last));
+        NodeIn xn = load_node(kargs(), load_desc<SLOW>(kargs(), min(gw + nw, last)));
+        uint32_t d = load_desc<SLOW>(kargs(), min(gw + 2 * nw, last));
         for (uint32_t i = gw; i < na; i += nw) {
             STAMP(w, 24);
             begin_node(w, x, y);
@@ -1733,7 +1741,7 @@ __global__ void __launch_bounds__(256, PSIM_WAVES_PER_SIMD) k_consume(RoundArgs 
             NodeX yn = load_x(kargs(), xn);
             writeback(w);
             NodeIn xnn = load_node(kargs(), d);
-            d = load_desc(kargs(), min(i + 3 * nw, last));
+            d = load_desc<SLOW>(kargs(), min(i + 3 * nw, last));
             x = xn; y = yn; xn = xnn;
         }
     }
@@ -1743,7 +1751,10 @@ __global__ void __launch_bounds__(256, PSIM_WAVES_PER_SIMD) k_consume(RoundArgs 
     flush_wave_stats(w, sst);
     __syncthreads();
     for (int i = threadIdx.x; i < NST; i += blockDim.x)
-        kargs().stat_part[(size_t)blockIdx.x * NST + i] = sst[i];
+        kargs().stat_part[(size_t)bid * NST + i] = sst[i];
+}
+__global__ void __launch_bounds__(256, PSIM_WAVES_PER_SIMD) k_consume(RoundArgs args) {
+    consume_blocks<false>(args, blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------ shuffle-exchange phase --
@@ -2557,7 +2568,7 @@ DEV void topk_insert(uint64_t (&K)[SHUF_TOPK], uint32_t (&E)[SHUF_TOPK], uint64_
     }
 }
 
-__global__ void __launch_bounds__(256) k_shuf(RoundArgs) {
+DEV void shuf_blocks(const uint32_t bid, const uint32_t nblk) {   // (block bid of nblk, as consume_blocks)
     if (*kargs().ctl) return;                         // an aborted batch (run_batch)
     enum { S_SHUF, S_FAIL, S_DIGEST, S_BOUND, S_N };
     __shared__ unsigned long long sst[S_N];
@@ -2567,7 +2578,7 @@ __global__ void __launch_bounds__(256) k_shuf(RoundArgs) {
     const uint32_t ns = *kargs().n_shuf;
     const uint64_t two58 = 1ull << 58;
     unsigned long long v[S_N] = {};
-    for (uint32_t P = blockIdx.x * blockDim.x + threadIdx.x; P < ns; P += gridDim.x * blockDim.x) {
+    for (uint32_t P = bid * blockDim.x + threadIdx.x; P < ns; P += nblk * blockDim.x) {
         KArgs& a = kargs();
         const uint4 D = a.desc_shuf[P];
         const uint32_t id = D.x;
@@ -2676,10 +2687,48 @@ __global__ void __launch_bounds__(256) k_shuf(RoundArgs) {
         for (int k = 0; k < S_N; k++)
             if (v[k]) atomicAdd(&sst[k], v[k]);
     __syncthreads();
-    uint64_t* row = kargs().stat_shuf + (size_t)blockIdx.x * NST;
+    uint64_t* row = kargs().stat_shuf + (size_t)bid * NST;
     for (uint32_t k = threadIdx.x; k < NST; k += blockDim.x)
         row[k] = k == ST_EMIT + PSIM_MSG_SHUFFLE ? sst[S_SHUF] : k == ST_FAIL ? sst[S_FAIL]
                : k == ST_DIGEST ? sst[S_DIGEST] : k == ST_BOUND ? sst[S_BOUND] : 0ull;
+}
+__global__ void __launch_bounds__(256) k_shuf(RoundArgs) { shuf_blocks(blockIdx.x, gridDim.x); }
+
+// --------------------------------------------- the HyParView phase, fused --
+// k_hv_phase: k_shuf's, k_consume's and k_lite_quarter's bodies in one launch,
+// each on its own range of logical blocks -- [0, sgrid) shuffle starts,
+// [sgrid, sgrid + cgrid) k_consume's list, the rest the lite list (none:
+// PSIM_PHASE_FUSED=2 launches k_lite_quarter after this).  The three take
+// k_relay's disjoint lists and write only their own nodes' rows, outbox
+// regions and stats rows (phase_consume), so they need no order among them;
+// one launch runs them side by side with no event fork and join, which cost
+// more than the overlap gave (profiles/r05/ab_log.txt r6s).  Each body sees
+// its range as its grid -- the same strides, the same stats rows as its own
+// kernel.  A block's registers and LDS are the largest body's and the sum of
+// the three carves; the launch bounds are the lite kernel's, whose occupancy
+// decides.
+// The hardware hands out blocks in index order, and the lite range takes the
+// first indices: the two short lists' blocks (mostly empty; a few hundred
+// heavy nodes' waves, ~40 dependent Philox draws a shuffle lane) then start
+// in the slots the lite kernel's last generation leaves as it drains.  With
+// the two chains first (PSIM_PHASE_ORDER=0) every live k_shuf block held one
+// of a CU's four block slots from the start and the phase was 5 us longer
+// (profiles/phase_fused/ab_log.txt).
+static_assert(PSIM_QUARTER_WPB == WAVES_PER_BLOCK, "one block size for the three bodies");
+#ifndef PSIM_PHASE_ORDER      // (0: k_shuf's and k_consume's blocks first, then the lite blocks, for A/B)
+#define PSIM_PHASE_ORDER 1
+#endif
+__global__ void __launch_bounds__(64 * PSIM_QUARTER_WPB, PSIM_QUARTER_WAVES)
+k_hv_phase(RoundArgs args, const uint32_t sgrid, const uint32_t cgrid) {
+    const uint32_t lgrid = gridDim.x - sgrid - cgrid;
+#if PSIM_PHASE_ORDER == 1     // the lite range takes the first block indices
+    const uint32_t b = blockIdx.x < lgrid ? blockIdx.x + sgrid + cgrid : blockIdx.x - lgrid;
+#else
+    const uint32_t b = blockIdx.x;
+#endif
+    if (b < sgrid) shuf_blocks(b, sgrid);
+    else if (b < sgrid + cgrid) consume_blocks<true>(args, b - sgrid, cgrid);
+    else lite::lite_kernel<16>(b - sgrid - cgrid, lgrid);
 }
 
 // ---------------------------------------------------- Plumtree lanes --
@@ -3363,6 +3412,11 @@ int debug_stamps(unsigned long long* out) {
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamps_lite), z, sizeof z) != hipSuccess) return -1;
     // k_lite_quarter's / k_lite_half's, when one ran (psim_lite.hip): 96 entries
     if (debug_stamps_half(out + 64) != 32) return -1;
+    // ... plus k_hv_phase's lite blocks (this TU's copy of psim_lite.h's sums)
+    unsigned long long f[32];
+    if (hipMemcpyFromSymbol(f, HIP_SYMBOL(lite::g_stamps_half), sizeof f) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(lite::g_stamps_half), z, sizeof z) != hipSuccess) return -1;
+    for (int k = 0; k < 32; k++) out[64 + k] += f[k];
     return 96;
 }
 #else

@@ -2700,6 +2700,9 @@ args:
     return PSIM_OK;
 }
 
+// PSIM_PHASE_FUSED's default (phase_consume)
+constexpr int PHASE_FUSED_DEFAULT = 3;
+
 void launch_lite(psim_handle* h, Shard* s, const RoundArgs& a, hipStream_t st) {
     h->lite.kernel<<<s->lgrid, h->lite.block, 0, st>>>(a);
 }
@@ -2754,7 +2757,23 @@ int phase_consume(psim_handle* h, Shard* s, RoundArgs& a) {
         static const bool conc_env = getenv("PSIM_CONCURRENT_PHASE") != nullptr;
         static const bool serial_env = getenv("PSIM_SERIAL_PHASE") != nullptr;
         const bool serial = serial_env || a.crash_round || !(conc_env || h->lite.side_by_side);
-        if (serial) {
+        // One launch for the three (k_hv_phase: each body on its own range
+        // of blocks; no fork, no join, no side streams) outside crash rounds,
+        // with k_lite_quarter's body only.  PSIM_PHASE_FUSED=3: all three;
+        // =2: k_shuf and k_consume, then k_lite_quarter alone; =0: the three
+        // launches (A/B); PSIM_SERIAL_PHASE and
+        // PSIM_CONCURRENT_PHASE keep their own paths
+        static const int fused_env = [] {
+            const char* e = getenv("PSIM_PHASE_FUSED");
+            const int v = e && *e ? atoi(e) : PHASE_FUSED_DEFAULT;
+            return v == 2 || v == 3 ? v : 0;
+        }();
+        const bool fused = fused_env && !a.crash_round && !serial_env && !conc_env && h->lite.kernel == k_lite_quarter;
+        if (fused) {
+            const uint32_t lg = fused_env == 3 ? s->lgrid : 0;
+            if (s->sgrid + s->cgrid + lg) k_hv_phase<<<s->sgrid + s->cgrid + lg, BLK, 0, s->stream>>>(a, s->sgrid, s->cgrid);
+            if (fused_env == 2) launch_lite(h, s, a, s->stream);
+        } else if (serial) {
             k_shuf<<<s->sgrid, BLK, 0, s->stream>>>(a);
             launch_lite(h, s, a, s->stream);
             k_consume<<<s->cgrid, BLK, 0, s->stream>>>(b);

@@ -165,6 +165,10 @@ __global__ void k_shuf(RoundArgs args);
 __global__ void k_consume_lite(RoundArgs args);
 __global__ void k_lite_half(RoundArgs args);
 __global__ void k_lite_quarter(RoundArgs args);
+// k_shuf's, k_consume's and k_lite_quarter's bodies on the block ranges
+// [0, sgrid), [sgrid, sgrid + cgrid) and the rest (psim_consume.hip); `args`
+// is the round's (k_relay's), with k_consume's list in desc_slow / n_slow
+__global__ void k_hv_phase(RoundArgs args, uint32_t sgrid, uint32_t cgrid);
 struct LiteKernel {
     void (*kernel)(RoundArgs);
     uint32_t block;             // threads per block

@@ -3,10 +3,13 @@ from a FETCH_SIZE pass and a WRITE_SIZE pass of that same command
 (profiles/run_pmc.sh).  Appends / replaces the record in
 profiles/pmc_records.json, which bench.py reads back by its pmc_key.
 
-Window: the `steps` timed rounds are the dispatches of each kernel before the
-overlay-drain rounds bench.py runs after its window (overlay.rounds_drained).
+Window: the `steps` timed rounds are the dispatches from k_relay's first timed
+one up to the overlay-drain rounds bench.py runs after its window
+(overlay.rounds_drained); without a k_relay (the pluggable lines) the last
+`steps` dispatches of each kernel before the drain.
 Per round: the sum over the node-round kernels (k_relay, k_shuf, k_lite_half
-or k_consume_lite, k_consume, k_ptq or k_ptl, k_pt; k_consume_pl for the
+or k_consume_lite, k_consume -- or k_hv_phase, the one launch that runs the
+bodies of the three (PSIM_PHASE_FUSED) -- k_ptq or k_ptl, k_pt; k_consume_pl for the
 pluggable lines B and D, which drain no rounds after their window).
 
 Units and corrections (profiles/calib/, measured on this MI355X): FETCH_SIZE
@@ -22,8 +25,8 @@ import json
 import os
 import sys
 
-KERNELS = ("k_relay(", "k_shuf(", "k_consume_lite(", "k_lite_half(", "k_lite_quarter(", "k_term(", "k_consume(", "k_ptl(", "k_ptq(",
-           "k_pt(", "k_consume_pl(")
+KERNELS = ("k_relay(", "k_hv_phase(", "k_shuf(", "k_consume_lite(", "k_lite_half(", "k_lite_quarter(", "k_term(", "k_consume(",
+           "k_ptl(", "k_ptq(", "k_pt(", "k_consume_pl(")
 
 
 def per_round(path, steps, tail, by=None):
@@ -31,10 +34,18 @@ def per_round(path, steps, tail, by=None):
     per kernel"""
     rows = list(csv.DictReader(open(path)))
     tot = 0.0
+    # k_relay runs once every round of a HyParView handle: the timed rounds'
+    # dispatches are those from the first timed k_relay up to the first
+    # drained one (a kernel that runs only in some rounds -- k_shuf, the lite
+    # kernel and k_consume in crash rounds, k_hv_phase in the others -- has no
+    # last-`steps` dispatches of its own to count back from)
+    relay = sorted({int(r["Dispatch_Id"]) for r in rows if "k_relay(" in r["Kernel_Name"]})
+    span = (relay[len(relay) - tail - steps], relay[len(relay) - tail] if tail else float("inf")) \
+        if len(relay) >= tail + steps else None
     for k in KERNELS:
         kr = [r for r in rows if k in r["Kernel_Name"]]
         ids = sorted({int(r["Dispatch_Id"]) for r in kr})
-        keep = set(ids[len(ids) - tail - steps:len(ids) - tail])
+        keep = set(i for i in ids if span[0] <= i < span[1]) if span else set(ids[len(ids) - tail - steps:len(ids) - tail])
         b = sum(float(r["Counter_Value"]) for r in kr if int(r["Dispatch_Id"]) in keep) * 1024 / steps
         tot += b
         if by is not None and b:
@@ -54,6 +65,13 @@ def main():
     counted = dict(by)
     if "k_lite_quarter" in by and "k_lite_half" not in by:
         counted["k_lite_half"] = by["k_lite_quarter"]
+    # k_hv_phase runs k_shuf's and k_consume's bodies, and the lite kernel's
+    # unless that was launched by itself (PSIM_PHASE_FUSED=2): its algorithmic
+    # bytes are the sum of theirs
+    alg = dict(bench.get("per_kernel_alg") or {})
+    if alg and "k_hv_phase" in by:
+        parts = ["k_shuf", "k_consume"] + ([] if "k_lite_half" in counted else ["k_lite_half"])
+        alg["k_hv_phase"] = sum(alg.get(k) or 0.0 for k in parts)
     rec = {"key": bench["pmc_key"],
            "traffic_per_launch": fetch + write,
            "traffic_upper_per_launch": 2 * fetch + write,
@@ -62,9 +80,8 @@ def main():
            "per_kernel": by,              # FETCH_SIZE + WRITE_SIZE per round, by kernel
            # each kernel's algorithmic bytes per round (bench.py --kernel-counts:
            # its own nodes processed, deliveries, emissions) and counted / algorithmic
-           "per_kernel_alg": bench.get("per_kernel_alg"),
-           "per_kernel_excess": ({k: counted[k] / a for k, a in bench["per_kernel_alg"].items() if a and k in counted}
-                                 if bench.get("per_kernel_alg") else None),
+           "per_kernel_alg": alg or None,
+           "per_kernel_excess": {k: counted[k] / a for k, a in alg.items() if a and k in counted} if alg else None,
            "source": "FETCH_SIZE + WRITE_SIZE per timed round of the node-round kernels, separate "
                      "rocprofv3 --pmc passes of this command (profiles/run_pmc.sh); FETCH_SIZE uncorrected: "
                      "random 64-B requests count exactly (profiles/calib/)"}

@@ -8,8 +8,8 @@ import json
 import sys
 from collections import defaultdict
 
-KERNELS = ["k_relay", "k_shuf", "k_consume_lite", "k_lite_half", "k_lite_quarter", "k_term", "k_consume", "k_ptl", "k_ptq", "k_pt",
-           "k_consume_pl"]
+KERNELS = ["k_relay", "k_hv_phase", "k_shuf", "k_consume_lite", "k_lite_half", "k_lite_quarter", "k_term", "k_consume", "k_ptl",
+           "k_ptq", "k_pt", "k_consume_pl"]
 
 
 def kname(s):

@@ -1,7 +1,8 @@
 """Per-round device time of every kernel over the bench's timed rounds, from a
 rocprofv3 kernel trace: the window opens at the STEPS-th last k_consume
-dispatch (the timed rounds come last) and each kernel's summed duration is
-divided by STEPS.  Also the window's wall span per round (gaps included).
+dispatch -- or k_hv_phase, the launch that runs its body in a round without
+crashes (PSIM_PHASE_FUSED) -- (the timed rounds come last) and each kernel's
+summed duration is divided by STEPS.  Also the window's wall span per round (gaps included).
 Rounds after the window (bench's overlay drain, `--tail`, from the bench
 line's overlay.rounds_drained) are excluded.
 Usage: python profiles/steady_kernels.py run_kernel_trace.csv [--steps 50] [--tail 40]"""
@@ -27,7 +28,7 @@ def main():
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     tail = int(sys.argv[sys.argv.index("--tail") + 1]) if "--tail" in sys.argv else 0
-    cons = [i for i, r in enumerate(rows) if "k_consume(" in r["Kernel_Name"]]
+    cons = [i for i, r in enumerate(rows) if "k_consume(" in r["Kernel_Name"] or "k_hv_phase(" in r["Kernel_Name"]]
     if tail:
         cons = cons[:-tail]
     first = cons[-steps]
@@ -50,7 +51,7 @@ def main():
         print("per round (us): k_relay k_consume k_pt")
         cur = {}
         for r in win:
-            k = short(r["Kernel_Name"]).replace("psim::", "")
+            k = short(r["Kernel_Name"]).replace("psim::", "").replace("k_hv_phase", "k_consume")
             if k in ("k_relay", "k_consume", "k_pt"):
                 cur[k] = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
                 if k == "k_pt" or (k == "k_consume" and "k_pt" not in cur and False):
