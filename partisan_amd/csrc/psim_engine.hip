@@ -2533,11 +2533,13 @@ struct RoundCtl {
 };
 
 // events + prepare for one shard; leaves `a` ready for k_consume.
-// events = false: the round's events were applied already (the redo of a
-// batch round, run_batch); batched: no host wait -- the outbox and route
+// events = false: no events to apply -- a batch's later rounds, or (redo) the
+// round's events were applied already by the attempt k_desc stopped (run_batch,
+// run_batch_ranked: they are still pending on the host, and the round is an
+// event round all the same); batched: no host wait -- the outbox and route
 // capacities stand and k_desc checks the outbox on the device (desc_cap)
 int phase_events_prepare(psim_handle* h, Shard* s, const RoundCtl& ctl, RoundArgs& a, bool events = true,
-                         bool batched = false) {
+                         bool batched = false, bool redo = false) {
     const uint32_t n = s->n;
     if (events && h->faults_dirty) {    // interposition funs installed / removed
         std::vector<uint64_t> keys(h->nx_omit_s.begin(), h->nx_omit_s.end());
@@ -2553,12 +2555,16 @@ int phase_events_prepare(psim_handle* h, Shard* s, const RoundCtl& ctl, RoundArg
     a.crash_round = ctl.crashes;
     // the up-and-partition pairs change only with crash, start and partition
     // events (k_crash, k_join, the partition copy): rebuilt only then
+    // (a redo: the stopped attempt's k_node_prep rebuilt them, after its
+    // events and before its k_desc set the abort word; nothing changed since)
     a.upart_dirty = !s->upart_valid ||
                     (events && (ctl.crashes || !h->pend_join.empty() || h->pend_part_set || h->pend_part_clear));
     // (a crash only disconnects, and a restarted peer's holders dropped it
     // in the EXIT of its crash round: neither wakes a quiet node)
-    a.lazy_wake = !s->upart_valid || (events && (h->pend_part_set || h->pend_part_clear || h->faults_dirty ||
-                                                 !h->pend_lv_a.empty()));
+    // (a redo wakes them as the stopped attempt would have: no node ran in
+    // it, so the quiet ones are quiet still, and the event is in force)
+    a.lazy_wake = !s->upart_valid || ((events || redo) && (h->pend_part_set || h->pend_part_clear ||
+                                                            h->faults_dirty || !h->pend_lv_a.empty()));
     s->upart_valid = true;
     if (events) {
         KTimer t(h, s, KT_EVENTS);
@@ -3238,7 +3244,7 @@ int run_round(psim_handle* h, uint64_t* st, bool events_applied = false, bool fr
     for (Shard* s : h->shards) s->tn = 0;        // (timers of a round that failed)
     std::vector<RoundArgs> args(h->shards.size());   // (consume fills the payload arena fields)
     for (size_t i = 0; i < h->shards.size() && !from_partition; i++)
-        TRY(phase_events_prepare(h, h->shards[i], ctl, args[i], !events_applied));
+        TRY(phase_events_prepare(h, h->shards[i], ctl, args[i], !events_applied, false, events_applied));
     // (test hook: this round fails half-way, after its events went to the
     // device, as an allocation failure inside a round would)
     static const long long fail_round = getenv("PSIM_TEST_FAIL_ROUND") ? atoll(getenv("PSIM_TEST_FAIL_ROUND")) : -1;
@@ -3389,6 +3395,28 @@ bool batchable(psim_handle* h) {
     return h->G == 1 && s->reserved && s->rcap && s->outbox.n;
 }
 
+// The outbox capacity a batch's k_desc checks against.  (test hook
+// PSIM_TEST_DESC_CAP=<slots>[@<rank>], read once per process: at most that
+// many slots -- on that shard_rank only, if given -- so a batch stops at
+// k_desc at will (slots = 1: every batch at its first round).  The outbox
+// keeps its size: the growth after the stop changes nothing and the redo is
+// run_round's, as after a real stop.  Batching stays on.)
+uint64_t batch_desc_cap(const psim_handle* h, const Shard* s) {
+    static const struct Hook {
+        uint64_t slots = 0;
+        long rank = -1;
+        Hook() {
+            const char* e = getenv("PSIM_TEST_DESC_CAP");
+            if (!e) return;
+            slots = strtoull(e, nullptr, 10);
+            if (const char* at = strchr(e, '@')) rank = atol(at + 1);
+        }
+    } hook;
+    const uint64_t real = std::min<uint64_t>(s->outbox.n, s->okey.n);
+    if (!hook.slots || (hook.rank >= 0 && hook.rank != h->rank)) return real;
+    return std::min<uint64_t>(real, hook.slots);
+}
+
 // Up to BATCH_MAX rounds enqueued back to back with no host wait between
 // them (the pending events go with the first), then one wait.  A round
 // whose outbox bound passes the outbox capacity (k_desc, code 1) or whose
@@ -3407,7 +3435,7 @@ int run_batch(psim_handle* h, uint32_t nb, psim_round_stats* st_out, uint32_t* d
     const std::vector<uint32_t> none;
     const bool bc0 = !h->pend_b_root.empty();
     s->tn = 0;
-    s->desc_cap = std::min<uint64_t>(s->outbox.n, s->okey.n);
+    s->desc_cap = batch_desc_cap(h, s);
     const auto t_enq = std::chrono::steady_clock::now();
     for (uint32_t j = 0; j < nb; j++) {
         s->stat_slot = j + 1;
@@ -3546,7 +3574,7 @@ int run_batch_ranked(psim_handle* h, uint32_t nb, psim_round_stats* st_out, uint
     const std::vector<uint32_t> none;
     const bool bc0 = !h->pend_b_root.empty();
     s->tn = 0;
-    s->desc_cap = std::min<uint64_t>(s->outbox.n, s->okey.n);
+    s->desc_cap = batch_desc_cap(h, s);
     const auto t_enq = std::chrono::steady_clock::now();
     double tph[5] = {0, 0, 0, 0, 0};                  // (PSIM_TRACE_BATCH: host ms per phase)
     auto tick = [](std::chrono::steady_clock::time_point& t0, double& acc) {
@@ -4842,6 +4870,11 @@ int psim_restore(psim_handle* h, const void* buf, size_t size) {
         if (s->n_stop.p) HIP_TRY(hipMemset(s->n_stop.p, 0, s->n_stop.n * sizeof(uint32_t)));
         s->reserved = false;
         s->upart_valid = false;
+        // (a rank's exchange capacities and batch length came from this
+        // handle's own traffic: the first round after a restore is exact and
+        // sets them from the all-reduced counts, alike on every rank)
+        s->xcap_h = s->xcap_t = 0;
+        s->xbatch = 1;
     }
     h->round = hd.round; h->tracked_msg = hd.tracked_msg;
     memcpy(h->slot_tab, hd.slot_tab, sizeof h->slot_tab);

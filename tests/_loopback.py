@@ -103,6 +103,16 @@ class LoopbackRanks:
         p = self._owned("delivery", first, count)
         return tuple(np.concatenate([x[i] for x in p]) for i in range(3))
 
+    # ---- snapshots: one per rank (its own rows), restored rank by rank into
+    # a world of the same size
+    def snapshot(self):
+        return [s.snapshot() for s in self.ranks]
+
+    def restore(self, snaps):
+        assert len(snaps) == self.world
+        for s, data in zip(self.ranks, snaps):
+            s.restore(data)
+
     def close(self):
         for s in self.ranks:
             s.close()

@@ -4,7 +4,7 @@ API calls, so two backends can be compared round by round."""
 import numpy as np
 
 from partisan_amd import workloads as W
-from partisan_amd.sim import default_config
+from partisan_amd.sim import _Driver, default_config
 
 STAT_FIELDS = ["emitted", "delivered", "dropped", "nodes_up", "nodes_processed", "exits",
                "send_fail", "first_deliveries", "overflow", "overflow_by", "digest", "omitted"]
@@ -210,6 +210,105 @@ def out_tail(make, n=512, seed=3, period=2, part_on=40, part_off=80, rounds=110,
             state["k"] += 1
     st = sim.run_schedule(W.doubling_join(n, seed), rounds, extra=hook)
     return sim, st, snaps
+
+
+def heal_after_quiet(make, n=512, seed=3, **cfg):
+    """A heal that wakes quiet nodes, as the first round of a multi-round
+    step.  Doubling bootstrap to round 30; a broadcast from node 0 every
+    round over rounds 30-59, a half/half partition from round 40: the lazy
+    pushes across it stay outstanding, and once a node's tick reaches no peer
+    it goes quiet (its later ticks only count failed sends).  Rounds 60-67
+    are quiet (step(7), step(1)); the heal starts step(8): round 68 wakes
+    every quiet node at once (at n = 512, seed 3: send_fail 7870, 7976 and
+    676, 623 messages in rounds 66, 67; 8593 and 17461 messages in rounds 68,
+    69).  Then, each at the start of a multi-round step: a partition with a
+    broadcast from another root, a crash wave, a heal with the crashed nodes'
+    rejoin and a broadcast, a second crash wave, a revive with a broadcast:
+    113 rounds.  The outstanding tables stay below PSIM_PT_OUT_CAP (no
+    overflow at the defaults)."""
+    sim = make(default_config(n_nodes=n, seed=seed, **cfg))
+    st = [sim.run_schedule(W.doubling_join(n, seed), 30)]
+    for k in range(30):
+        if k == 10:
+            sim.set_partition(W.half_partition(n))
+        sim.broadcast(0, k)
+        st.append(sim.step(1))
+    st.append(sim.step(7))
+    st.append(sim.step(1))
+    sim.clear_partition()
+    st.append(sim.step(8))                      # rounds 68-75: the heal first
+    rng = np.random.Generator(np.random.PCG64([seed, 41]))
+    ids = np.arange(2, n, dtype=np.uint32)      # (nodes 0 and 1 stay: the roots and the rejoin contact)
+    wave1 = np.sort(rng.choice(ids, size=n // 16, replace=False)).astype(np.uint32)
+    wave2 = np.sort(rng.choice(np.setdiff1d(ids, wave1), size=n // 16, replace=False)).astype(np.uint32)
+    sim.set_partition(W.half_partition(n))
+    sim.broadcast(1, 30)
+    st.append(sim.step(8))                      # 76-83
+    sim.crash(wave1)
+    st.append(sim.step(7))                      # 84-90
+    sim.clear_partition()
+    sim.join(wave1, np.zeros(wave1.size, np.uint32))
+    sim.broadcast(0, 31)
+    st.append(sim.step(8))                      # 91-98
+    sim.crash(wave2)
+    st.append(sim.step(6))                      # 99-104
+    sim.revive(wave2)
+    sim.broadcast(1, 32)
+    st.append(sim.step(8))                      # 105-112
+    return sim, np.concatenate(st)
+
+
+def resuming(make, at, target="fresh"):
+    """`make` whose handle, when a step reaches round `at`, is snapshotted and
+    closed, and the run carried on by a second handle that restored the
+    snapshot (psim_snapshot / psim_restore).  A step across `at` is split
+    there and its stats concatenated.  The second handle comes from the same
+    `make` and a copy of the config; target="used": it first runs 10 rounds
+    of the same doubling bootstrap and a broadcast, so that its buffers,
+    capacities and per-round words are not a fresh handle's."""
+    assert target in ("fresh", "used")
+
+    class Resuming:
+        def __init__(self, cfg):
+            self._cfg = type(cfg).from_buffer_copy(cfg)
+            # (the comm id is a pointer the first handle owns: each handle gets its own)
+            self._cfg.comm_id = None
+            self._sim = make(cfg)
+            self.resumed = False
+
+        def __getattr__(self, name):
+            return getattr(self._sim, name)
+
+        @property
+        def round(self):
+            return self._sim.round
+
+        def _resume(self):
+            snap = self._sim.snapshot()
+            cfg = type(self._cfg).from_buffer_copy(self._cfg)
+            other = make(cfg)
+            if target == "used":
+                other.run_schedule(W.doubling_join(cfg.n_nodes, cfg.seed), 9)
+                other.broadcast(0, 1)
+                other.step(1)
+            other.restore(snap)
+            self._sim.close()
+            self._sim, self.resumed = other, True
+
+        def step(self, n_rounds=1):
+            r = self._sim.round
+            if self.resumed or not r <= at < r + n_rounds:
+                return self._sim.step(n_rounds)
+            st = [self._sim.step(at - r)] if r < at else []
+            self._resume()
+            st.append(self._sim.step(r + n_rounds - at))
+            return np.concatenate(st)
+
+        run_schedule = _Driver.run_schedule
+
+        def close(self):
+            self._sim.close()
+    return Resuming
 
 
 VARIANT = dict(max_active_size=8, max_passive_size=20, arwl=6, prwl=6, persist_epoch=1)
