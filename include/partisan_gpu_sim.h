@@ -556,8 +556,12 @@ int psim_wire_decode(const uint8_t *buf, size_t len, const psim_wire_names *name
  * kernel's share of the algorithmic bytes (bench.py --kernel-counts,
  * profiles/pmc_record.py).  With cap >= 28 a seventh entry, k_node_prep:
  * the quiet lazy ticks it counted without running their nodes (processed,
- * 0, 0, 0).  Returns 6 or 7 (0 under the pluggable
- * manager). */
+ * 0, 0, 0).  With cap >= 32 an eighth: the early part
+ * of k_ptl's list (the nodes whose HyParView phase k_relay finished) where it
+ * ran apart from the late one -- k_hv_phase's block range, or
+ * PSIM_PTL_EARLY=2's launch; zeros where one k_ptl launch ran both parts.
+ * The k_ptl entry is the sum of both parts either way.  Returns 6, 7 or 8
+ * (0 under the pluggable manager). */
 int psim_debug_kernel_counts(psim_handle *h, uint64_t *out, int cap);
 
 /* Per-kernel device time (ms) accumulated over the last psim_step call:

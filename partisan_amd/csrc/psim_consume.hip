@@ -1690,14 +1690,21 @@ DEV void writeback(Wv& w) {
 // node whose HyParView work is more than one SHUFFLE relay)
 // Block `bid` of `nblk`: the launch's own index and grid in k_consume, the
 // consume range's in k_hv_phase (SLOW: the list as k_relay's arguments name it).
+// The block's LDS, in words from a 16-byte aligned base (the caller carves:
+// the kernel's own array, or k_hv_phase's, which its ranges' bodies share).
+struct ConsumeCarve {
+    static constexpr uint32_t SCRATCH = NST * 2, NLOGS = SCRATCH + WAVES_PER_BLOCK * 64,
+                              SREC = (NLOGS + WAVES_PER_BLOCK * NLOG * (PSIM_ACTIVE_CAP + 1) + 3) & ~3u,
+                              SKEY = SREC + WAVES_PER_BLOCK * STAGE * 16, WORDS = SKEY + WAVES_PER_BLOCK * STAGE;
+};
 template <bool SLOW>
-DEV void consume_blocks(const RoundArgs& args, const uint32_t bid, const uint32_t nblk) {
+DEV void consume_blocks(const RoundArgs& args, const uint32_t bid, const uint32_t nblk, uint32_t* const pool) {
     if (*kargs().ctl) return;                         // an aborted batch (run_batch)
-    __shared__ uint64_t sst[NST];
-    __shared__ uint32_t scratch[WAVES_PER_BLOCK][64];
-    __shared__ uint32_t nlogs[WAVES_PER_BLOCK][NLOG * (PSIM_ACTIVE_CAP + 1)];
-    __shared__ __attribute__((aligned(16))) uint32_t srecs[WAVES_PER_BLOCK][STAGE * 16];
-    __shared__ uint32_t skeys[WAVES_PER_BLOCK][STAGE];
+    uint64_t* const sst = reinterpret_cast<uint64_t*>(pool);
+    uint32_t* const srecs = pool + ConsumeCarve::SREC;
+    uint32_t* const scratch = pool + ConsumeCarve::SCRATCH;
+    uint32_t* const nlogs = pool + ConsumeCarve::NLOGS;
+    uint32_t* const skeys = pool + ConsumeCarve::SKEY;
     for (int i = threadIdx.x; i < NST; i += blockDim.x) sst[i] = 0;
     __syncthreads();
 
@@ -1706,10 +1713,10 @@ DEV void consume_blocks(const RoundArgs& args, const uint32_t bid, const uint32_
     const uint32_t nw = nblk * WAVES_PER_BLOCK;
     Wv w;
     w.a = &args;
-    w.lds = scratch[wid];
-    w.nlog = nlogs[wid];
-    w.srec = srecs[wid];
-    w.skey = skeys[wid];
+    w.lds = scratch + wid * 64;
+    w.nlog = nlogs + wid * (NLOG * (PSIM_ACTIVE_CAP + 1));
+    w.srec = srecs + wid * (STAGE * 16);
+    w.skey = skeys + wid * STAGE;
     w.slots = nullptr;
 #ifdef PSIM_STAMPS
     __shared__ uint64_t stamps[WAVES_PER_BLOCK][32];
@@ -1754,7 +1761,8 @@ DEV void consume_blocks(const RoundArgs& args, const uint32_t bid, const uint32_
         kargs().stat_part[(size_t)bid * NST + i] = sst[i];
 }
 __global__ void __launch_bounds__(256, PSIM_WAVES_PER_SIMD) k_consume(RoundArgs args) {
-    consume_blocks<false>(args, blockIdx.x, gridDim.x);
+    __shared__ __attribute__((aligned(16))) uint32_t pool[ConsumeCarve::WORDS];
+    consume_blocks<false>(args, blockIdx.x, gridDim.x, pool);
 }
 
 // ------------------------------------------------ shuffle-exchange phase --
@@ -2223,7 +2231,7 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
     if (blockIdx.x == 0 && threadIdx.x == 0) kargs().ktime[0] = __builtin_amdgcn_s_memrealtime();
     enum { R_PROC, R_DELIV, R_SHUF, R_FAIL, R_DIGEST, R_BOUND, R_DELIV_FJ, R_FJ, R_N };
     __shared__ unsigned long long sst[R_N];
-    __shared__ uint32_t wc5[9][5];                    // per list: the wave counts, then the block's base
+    __shared__ uint32_t wc5[11][5];                   // per list: the wave counts, then the block's base
     if (threadIdx.x < R_N) sst[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t l = lane_id();
@@ -2390,46 +2398,55 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
         // hands k_pt the ones that do not fit a lane)
         const bool origin_node = ((D.z >> 28) & DESC_ORIGIN) != 0;
         {
-            // the seven lists at once: one barrier-separated count, the
-            // block atomics from seven lanes of one instruction (one after
+            // the lists at once: one barrier-separated count, the block
+            // atomics from eleven lanes of one instruction (one after
             // another they were serial L2 round trips per block step); k_ptl's
-            // list as two, BROADCAST nodes from its front, the others from
-            // its back (ptl_desc), and the lite list likewise by SHUFFLE
-            // terminals (lite_at)
+            // list in two parts -- early: this lane finishes the node's
+            // HyParView phase below, so its Plumtree phase depends on no
+            // kernel of that phase (k_hv_phase runs it beside them); late:
+            // a heavy, lite or k_shuf node, whose outbox count, draw counter
+            // and rows that phase still writes -- each part as two, BROADCAST
+            // nodes from its half's front, the others from its back
+            // (ptl_desc), and the lite list likewise by SHUFFLE terminals
+            // (lite_at)
             const bool ptl = P < na && to_pt && !origin_node, lt = P < na && lite;
+            const bool pe = ptl && (!a.ptl_split || (!heavy && !lite && !shuf)), pl = ptl && !pe;
+            const bool pb = bcast || !PSIM_PTL_BIN;
             const bool lt0 = lt && !(extra && PSIM_LITE_BIN), lt1 = lt && extra && PSIM_LITE_BIN;
             const bool tb = term || !PSIM_LITE_BIN;
-            const bool g[9] = {P < na && heavy, P < na && to_pt && origin_node, ptl && (bcast || !PSIM_PTL_BIN),
-                               P < na && shuf, lt0 && tb, ptl && !(bcast || !PSIM_PTL_BIN), lt0 && !tb,
-                               lt1 && tb, lt1 && !tb};
-            uint64_t m[9];
+            const bool g[11] = {P < na && heavy, P < na && to_pt && origin_node, pe && pb,
+                                P < na && shuf, lt0 && tb, pe && !pb, lt0 && !tb,
+                                lt1 && tb, lt1 && !tb, pl && pb, pl && !pb};
+            uint64_t m[11];
 #pragma unroll
-            for (int k = 0; k < 9; k++) m[k] = ballot(g[k]);
+            for (int k = 0; k < 11; k++) m[k] = ballot(g[k]);
             const uint32_t wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
             __syncthreads();                          // the previous step's readers of wc5 are done
             if (l == 0)
 #pragma unroll
-                for (int k = 0; k < 9; k++) wc5[k][wv] = popc(m[k]);
+                for (int k = 0; k < 11; k++) wc5[k][wv] = popc(m[k]);
             __syncthreads();
-            if (threadIdx.x < 9) {
+            if (threadIdx.x < 11) {
                 const uint32_t k = threadIdx.x;
                 uint32_t t = 0;
                 for (uint32_t j = 0; j < nwv; j++) t += wc5[k][j];
                 uint32_t* cnt = k == 0 ? a.n_slow : k == 1 ? a.n_pt : k == 2 ? a.n_ptl : k == 3 ? a.n_shuf
-                              : k == 4 ? a.n_lite : k == 5 ? a.n_ptl + 1 : a.n_lite + (k - 5);
+                              : k == 4 ? a.n_lite : k == 5 ? a.n_ptl + 1 : k < 9 ? a.n_lite + (k - 5)
+                              : a.n_ptl + (k - 7);
                 wc5[k][4] = t ? atomicAdd(cnt, t) : 0u;
             }
             __syncthreads();
 #pragma unroll
-            for (int k = 0; k < 9; k++)
+            for (int k = 0; k < 11; k++)
                 if (g[k]) {
                     uint32_t b0 = wc5[k][4];
                     for (uint32_t j = 0; j < wv; j++) b0 += wc5[k][j];
                     const uint32_t at = b0 + popc(m[k] & lt_mask());
-                    uint4* desc = k == 0 ? a.desc_slow : k == 1 ? a.desc_pt : k == 2 || k == 5 ? a.desc_ptl
+                    uint4* desc = k == 0 ? a.desc_slow : k == 1 ? a.desc_pt : k == 2 || k == 5 || k >= 9 ? a.desc_ptl
                                 : k == 3 ? a.desc_shuf : a.desc_lite;
                     const uint32_t nl = a.n_local;
-                    desc[k == 5 || k == 6 ? nl - 1 - at : k == 7 ? nl + at : k == 8 ? 2 * nl - 1 - at : at] =
+                    desc[k == 5 || k == 6 ? nl - 1 - at : k == 7 || k == 9 ? nl + at
+                         : k == 8 || k == 10 ? 2 * nl - 1 - at : at] =
                         k == 0 && maps ? make_uint4(D.x, D.y, D.z | DESC_MAPS_BIT, D.w) : D;
                 }
         }
@@ -2568,10 +2585,9 @@ DEV void topk_insert(uint64_t (&K)[SHUF_TOPK], uint32_t (&E)[SHUF_TOPK], uint64_
     }
 }
 
-DEV void shuf_blocks(const uint32_t bid, const uint32_t nblk) {   // (block bid of nblk, as consume_blocks)
+enum { S_SHUF, S_FAIL, S_DIGEST, S_BOUND, S_N };      // (the block's LDS: S_N sums, the caller's)
+DEV void shuf_blocks(const uint32_t bid, const uint32_t nblk, unsigned long long* const sst) {   // (block bid of nblk, as consume_blocks)
     if (*kargs().ctl) return;                         // an aborted batch (run_batch)
-    enum { S_SHUF, S_FAIL, S_DIGEST, S_BOUND, S_N };
-    __shared__ unsigned long long sst[S_N];
     if (threadIdx.x < S_N) sst[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t l = lane_id();
@@ -2692,43 +2708,9 @@ DEV void shuf_blocks(const uint32_t bid, const uint32_t nblk) {   // (block bid 
         row[k] = k == ST_EMIT + PSIM_MSG_SHUFFLE ? sst[S_SHUF] : k == ST_FAIL ? sst[S_FAIL]
                : k == ST_DIGEST ? sst[S_DIGEST] : k == ST_BOUND ? sst[S_BOUND] : 0ull;
 }
-__global__ void __launch_bounds__(256) k_shuf(RoundArgs) { shuf_blocks(blockIdx.x, gridDim.x); }
-
-// --------------------------------------------- the HyParView phase, fused --
-// k_hv_phase: k_shuf's, k_consume's and k_lite_quarter's bodies in one launch,
-// each on its own range of logical blocks -- [0, sgrid) shuffle starts,
-// [sgrid, sgrid + cgrid) k_consume's list, the rest the lite list (none:
-// PSIM_PHASE_FUSED=2 launches k_lite_quarter after this).  The three take
-// k_relay's disjoint lists and write only their own nodes' rows, outbox
-// regions and stats rows (phase_consume), so they need no order among them;
-// one launch runs them side by side with no event fork and join, which cost
-// more than the overlap gave (profiles/r05/ab_log.txt r6s).  Each body sees
-// its range as its grid -- the same strides, the same stats rows as its own
-// kernel.  A block's registers and LDS are the largest body's and the sum of
-// the three carves; the launch bounds are the lite kernel's, whose occupancy
-// decides.
-// The hardware hands out blocks in index order, and the lite range takes the
-// first indices: the two short lists' blocks (mostly empty; a few hundred
-// heavy nodes' waves, ~40 dependent Philox draws a shuffle lane) then start
-// in the slots the lite kernel's last generation leaves as it drains.  With
-// the two chains first (PSIM_PHASE_ORDER=0) every live k_shuf block held one
-// of a CU's four block slots from the start and the phase was 5 us longer
-// (profiles/phase_fused/ab_log.txt).
-static_assert(PSIM_QUARTER_WPB == WAVES_PER_BLOCK, "one block size for the three bodies");
-#ifndef PSIM_PHASE_ORDER      // (0: k_shuf's and k_consume's blocks first, then the lite blocks, for A/B)
-#define PSIM_PHASE_ORDER 1
-#endif
-__global__ void __launch_bounds__(64 * PSIM_QUARTER_WPB, PSIM_QUARTER_WAVES)
-k_hv_phase(RoundArgs args, const uint32_t sgrid, const uint32_t cgrid) {
-    const uint32_t lgrid = gridDim.x - sgrid - cgrid;
-#if PSIM_PHASE_ORDER == 1     // the lite range takes the first block indices
-    const uint32_t b = blockIdx.x < lgrid ? blockIdx.x + sgrid + cgrid : blockIdx.x - lgrid;
-#else
-    const uint32_t b = blockIdx.x;
-#endif
-    if (b < sgrid) shuf_blocks(b, sgrid);
-    else if (b < sgrid + cgrid) consume_blocks<true>(args, b - sgrid, cgrid);
-    else lite::lite_kernel<16>(b - sgrid - cgrid, lgrid);
+__global__ void __launch_bounds__(256) k_shuf(RoundArgs) {
+    __shared__ unsigned long long sst[S_N];
+    shuf_blocks(blockIdx.x, gridDim.x, sst);
 }
 
 // ---------------------------------------------------- Plumtree lanes --
@@ -2978,13 +2960,21 @@ DEV void ptl_ack_out(PtLane& n, uint64_t key) {
 // the precondition pass: a record load issued after the node's emissions
 // waits for those stores too (one vector memory counter, in order), so the
 // handler loop loads none of them
-constexpr int PTL_RREG = PSIM_PTL_RREG;
+// (a template argument of the body: k_hv_phase's early range runs it under
+// the lite kernel's 128 VGPRs with PSIM_PTL_RREG_RANGE of them, k_ptl alone
+// takes 168 VGPRs with 6; 2 measured 6 us a round faster in the range than 4,
+// profiles/ptl_early/ab_log.txt r2 -- the range is off by default either way)
+#ifndef PSIM_PTL_RREG_RANGE
+#define PSIM_PTL_RREG_RANGE 4
+#endif
+template <int PTL_RREG>
 struct PtlRecs {
     uint32_t src[PTL_RREG > 0 ? PTL_RREG : 1], tt[PTL_RREG > 0 ? PTL_RREG : 1], msg[PTL_RREG > 0 ? PTL_RREG : 1],
         rnd[PTL_RREG > 0 ? PTL_RREG : 1], root[PTL_RREG > 0 ? PTL_RREG : 1];
 };
 // record j's source, type word, message id, round and root
-DEV void ptl_rec(const KArgs& a, const PtlRecs& R, uint32_t base, uint32_t j, uint32_t& src, uint32_t& tt,
+template <int PTL_RREG>
+DEV void ptl_rec(const KArgs& a, const PtlRecs<PTL_RREG>& R, uint32_t base, uint32_t j, uint32_t& src, uint32_t& tt,
                  uint32_t& msg, uint32_t& rnd, uint32_t& root) {
     if (j < (uint32_t)PTL_RREG) {
         src = R.src[0]; tt = R.tt[0]; msg = R.msg[0]; rnd = R.rnd[0]; root = R.root[0];
@@ -3002,21 +2992,47 @@ DEV void ptl_rec(const KArgs& a, const PtlRecs& R, uint32_t base, uint32_t j, ui
 #else
 #define PTL_BOUNDS __launch_bounds__(PTL_BLK, PSIM_PTL_BLOCKS_PER_CU)
 #endif
-__global__ void PTL_BOUNDS k_ptl(RoundArgs) {
+enum { T_FIRST, T_FAIL, T_OVF, T_BOUND, T_DLV, T_EMT = T_DLV + 5, T_N = T_EMT + 5 };
+// The block's LDS, in words (the caller carves, as for consume_blocks): the
+// sums (+ the digest), the message slots, the lanes' tables.
+struct PtlCarve {
+    static constexpr uint32_t SLOTS = 2 * (T_N + 1), TABS = SLOTS + 2 * PSIM_MSG_SLOTS,
+                              WORDS = TABS + (2 * PTL_SET + 2 * PTL_CAP) * PTL_BLK;
+};
+// the block's threads meet: the block's barrier, or, in a block range of
+// k_hv_phase, whose blocks run this body in their first wave alone (ONE_WAVE),
+// that wave's LDS accesses in order
+template <bool ONE_WAVE>
+DEV void ptl_sync() {
+    if (ONE_WAVE) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    } else {
+        __syncthreads();
+    }
+}
+// Block `bid` of `nblk` over `part` of the list (PTL_BOTH / PTL_EARLY /
+// PTL_LATE, ptl_desc), the block being threads [0, PTL_BLK): k_ptl's launch,
+// or the early range of k_hv_phase (ONE_WAVE).  The early part's blocks leave
+// their stats in rows of their own (stat_ptle); a launch of both parts zeroes
+// those (the route sums every row every round).
+template <int PTL_RREG, bool ONE_WAVE>
+DEV void ptl_blocks(const uint32_t bid, const uint32_t nblk, const uint32_t part, uint32_t* const pool) {
+    static_assert(!ONE_WAVE || PTL_BLK == 64, "a block range of k_hv_phase runs k_ptl's body in one wave");
     if (*kargs().ctl) return;                         // an aborted batch (run_batch)
-    enum { T_FIRST, T_FAIL, T_OVF, T_BOUND, T_DLV, T_EMT = T_DLV + 5, T_N = T_EMT + 5 };
-    __shared__ unsigned long long sst[T_N + 1];       // (+ the digest)
-    __shared__ uint32_t sslots[2 * PSIM_MSG_SLOTS];
-    __shared__ uint32_t tabs[(2 * PTL_SET + 2 * PTL_CAP) * PTL_BLK];
-    for (int i = threadIdx.x; i < 2 * PSIM_MSG_SLOTS; i += blockDim.x) sslots[i] = kargs().slots[i];
+    unsigned long long* const sst = reinterpret_cast<unsigned long long*>(pool);
+    uint32_t* const sslots = pool + PtlCarve::SLOTS;
+    uint32_t* const tabs = pool + PtlCarve::TABS;
+    for (int i = threadIdx.x; i < 2 * PSIM_MSG_SLOTS; i += PTL_BLK) sslots[i] = kargs().slots[i];
     if (threadIdx.x < T_N + 1) sst[threadIdx.x] = 0;
 #ifdef PSIM_STAMPS
     __shared__ unsigned long long ptl_st[16];
     if (threadIdx.x < 16) ptl_st[threadIdx.x] = threadIdx.x == 15 ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-    __syncthreads();
+    ptl_sync<ONE_WAVE>();
     const uint32_t l = lane_id();
-    const uint32_t nq0 = kargs().n_ptl[0], nq = nq0 + kargs().n_ptl[1];
+    uint32_t nc[4], nq;
+    ptl_counts(kargs(), part, nc, nq);
     uint32_t v[T_N] = {};
     uint64_t dig = 0;
     const uint32_t X0[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -3025,16 +3041,16 @@ __global__ void PTL_BOUNDS k_ptl(RoundArgs) {
     n.LZ.p = tabs + PTL_SET * PTL_BLK + threadIdx.x;
     n.OL.p = tabs + 2 * PTL_SET * PTL_BLK + threadIdx.x;
     n.OH.p = tabs + (2 * PTL_SET + PTL_CAP) * PTL_BLK + threadIdx.x;
-    for (uint32_t base = blockIdx.x * blockDim.x; base < nq; base += gridDim.x * blockDim.x) {
+    for (uint32_t base = bid * PTL_BLK; base < nq; base += nblk * PTL_BLK) {
         KArgs& a = kargs();
         const uint32_t P = base + threadIdx.x;
         bool go = false, fall = false;
         uint4 D = make_uint4(0, 0, 0, 0);
-        PtlRecs R;
+        PtlRecs<PTL_RREG> R;
         uint32_t root0 = NONE, rtw4 = 0, rtw5 = 0, w10 = 0, w11 = 0, start = 0, act_n = 0, tmask = 0;
         uint16_t up[PSIM_ACTIVE_CAP];
         if (P < nq) {
-            D = ptl_desc(a, nq0, P);
+            D = ptl_desc(a, nc, P);
             const size_t li = D.x - a.lo;
             const uint32_t* hp = reinterpret_cast<const uint32_t*>(a.hdr + li);
             // (the active row and the partition byte with the node's rows:
@@ -3106,7 +3122,8 @@ __global__ void PTL_BOUNDS k_ptl(RoundArgs) {
             fall = !ok;
         }
         PTL_STAMP(0);
-        // nodes that do not fit go to k_pt's list: one atomic a wave (a block
+        // nodes that do not fit go to k_pt's list (k_pt runs after both parts
+        // of this list, whichever launch ran them): one atomic a wave (a block
         // is one wave), its return waited for only where the list entries are
         // written, after the node's handlers
         const uint64_t fm = ballot(fall);
@@ -3375,9 +3392,11 @@ __global__ void PTL_BOUNDS k_ptl(RoundArgs) {
             if (v[k]) atomicAdd(&sst[k], (unsigned long long)v[k]);
         if (dig) atomicAdd(&sst[T_N], (unsigned long long)dig);
     }
-    __syncthreads();
-    uint64_t* row = kargs().stat_ptl + (size_t)blockIdx.x * NST;
-    for (uint32_t k = threadIdx.x; k < NST; k += blockDim.x) {
+    ptl_sync<ONE_WAVE>();
+    uint64_t* row = (part == PTL_EARLY ? kargs().stat_ptle : kargs().stat_ptl) + (size_t)bid * NST;
+    uint64_t* zrow = part == PTL_BOTH && kargs().stat_ptle ? kargs().stat_ptle + (size_t)bid * NST : nullptr;
+    for (uint32_t k = threadIdx.x; k < NST; k += PTL_BLK) {
+        if (zrow) zrow[k] = 0;
         uint64_t x = 0;
         if (k == ST_FIRST) x = sst[T_FIRST];
         else if (k == ST_FAIL) x = sst[T_FAIL];
@@ -3390,6 +3409,86 @@ __global__ void PTL_BOUNDS k_ptl(RoundArgs) {
             x = sst[T_EMT + k - ST_EMIT - PSIM_MSG_PT_BROADCAST];
         row[k] = x;
     }
+}
+__global__ void PTL_BOUNDS k_ptl(RoundArgs) {
+    __shared__ __attribute__((aligned(16))) uint32_t pool[PtlCarve::WORDS];
+    ptl_blocks<PSIM_PTL_RREG, false>(blockIdx.x, gridDim.x, PTL_BOTH, pool);
+}
+__global__ void PTL_BOUNDS k_ptl_part(RoundArgs, const uint32_t part) {
+    __shared__ __attribute__((aligned(16))) uint32_t pool[PtlCarve::WORDS];
+    ptl_blocks<PSIM_PTL_RREG, false>(blockIdx.x, gridDim.x, part, pool);
+}
+
+// --------------------------------------------- the HyParView phase, fused --
+// k_hv_phase: k_shuf's, k_consume's and k_lite_quarter's bodies in one launch,
+// each on its own range of logical blocks -- [0, sgrid) shuffle starts,
+// [sgrid, sgrid + cgrid) k_consume's list, then the lite list (none:
+// PSIM_PHASE_FUSED=2 launches k_lite_quarter after this), then the last egrid
+// blocks, the early part of k_ptl's list (none: PSIM_PTL_EARLY=0 / 2,
+// phase_consume).  The three take k_relay's disjoint lists and write only
+// their own nodes' rows, outbox regions and stats rows (phase_consume), so
+// they need no order among them; one launch runs them side by side with no
+// event fork and join, which cost more than the overlap gave
+// (profiles/r05/ab_log.txt r6s).  Each body sees its range as its grid -- the
+// same strides, the same stats rows as its own kernel.  A block's registers
+// are the largest body's and its LDS the largest carve (one array, which the
+// range's body carves: static arrays of the inlined bodies would add up); the
+// launch bounds are the lite kernel's, whose occupancy decides.
+// The early range: the Plumtree phase of the nodes whose HyParView phase
+// k_relay's lane finished (no heavy, lite or k_shuf node: k_relay's bins), so
+// nothing the other ranges write is theirs, and k_ptl's body reads of another
+// node only its up-and-partition pair, which no kernel of the phase writes.
+// A range block runs the body in its first wave (k_ptl is a one-wave block:
+// psim_kernels.h PTL_BLOCK); the other three return at once and free their
+// slots.  The late part runs in k_ptl's own launch after this one.
+// The hardware hands out blocks in index order, and the lite range takes the
+// first indices: the two short lists' blocks (mostly empty; a few hundred
+// heavy nodes' waves, ~40 dependent Philox draws a shuffle lane) then start
+// in the slots the lite kernel's last generation leaves as it drains.  With
+// the two chains first (PSIM_PHASE_ORDER=0) every live k_shuf block held one
+// of a CU's four block slots from the start and the phase was 5 us longer
+// (profiles/phase_fused/ab_log.txt).  The early range's place is
+// PSIM_PTL_ORDER (profiles/ptl_early/ab_log.txt): 0 the last indices, after
+// the short lists; 1 the first, before the lite range; 2 one early block
+// after every q - 1 lite blocks, q = (lgrid + egrid) / egrid.
+static_assert(PSIM_QUARTER_WPB == WAVES_PER_BLOCK, "one block size for the bodies");
+#ifndef PSIM_PHASE_ORDER      // (0: k_shuf's and k_consume's blocks first, then the lite blocks, for A/B)
+#define PSIM_PHASE_ORDER 1
+#endif
+#ifndef PSIM_PTL_ORDER
+#define PSIM_PTL_ORDER 0
+#endif
+constexpr uint32_t cmax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+constexpr uint32_t PHASE_LDS_WORDS = cmax(cmax(2 * S_N, ConsumeCarve::WORDS), cmax(lite::Carve<16>::WORDS, PtlCarve::WORDS));
+static_assert(PHASE_LDS_WORDS * 4 <= 19456, "k_hv_phase's LDS a block: no more than the three bodies' sum was");
+__global__ void __launch_bounds__(64 * PSIM_QUARTER_WPB, PSIM_QUARTER_WAVES)
+k_hv_phase(RoundArgs args, const uint32_t sgrid, const uint32_t cgrid, const uint32_t egrid) {
+    __shared__ __attribute__((aligned(16))) uint32_t pool[PHASE_LDS_WORDS];
+    const uint32_t lgrid = gridDim.x - sgrid - cgrid - egrid, hv = sgrid + cgrid;
+    // p: the block's index with the early range's blocks taken out (PSIM_PHASE_ORDER's), or NONE for one of those
+    uint32_t p = blockIdx.x, e = NONE;
+#if PSIM_PTL_ORDER == 1
+    if (p < egrid) { e = p; p = NONE; } else p -= egrid;
+#elif PSIM_PTL_ORDER == 2
+    if (egrid) {
+        const uint32_t q = (lgrid + egrid) / egrid, k = min(p / q, egrid);
+        if (p % q == q - 1 && p / q < egrid) { e = p / q; p = NONE; } else p -= k;
+    }
+#else
+    if (p >= hv + lgrid) { e = p - hv - lgrid; p = NONE; }
+#endif
+    if (p == NONE) {
+        if (threadIdx.x < PTL_BLK) ptl_blocks<PSIM_PTL_RREG_RANGE, true>(e, egrid, PTL_EARLY, pool);
+        return;
+    }
+#if PSIM_PHASE_ORDER == 1     // the lite range takes the first block indices
+    const uint32_t b = p < lgrid ? p + hv : p - lgrid;
+#else
+    const uint32_t b = p;
+#endif
+    if (b < sgrid) shuf_blocks(b, sgrid, reinterpret_cast<unsigned long long*>(pool));
+    else if (b < hv) consume_blocks<true>(args, b - sgrid, cgrid, pool);
+    else lite::lite_kernel<16>(b - hv, lgrid, pool);
 }
 
 uint32_t consume_grid() { return resident_grid((const void*)k_consume, WAVES_PER_BLOCK * 64); }

@@ -1214,7 +1214,7 @@ __global__ void __launch_bounds__(BLK) k_node_prep(RoundArgs a, const unsigned l
         a.ktime[0] = ~0ull; a.ktime[1] = 0; *a.n_slow = 0; *a.n_pt = 0;
         if (a.n_shuf) *a.n_shuf = 0;
         if (a.n_lite) { a.n_lite[0] = 0; a.n_lite[1] = 0; a.n_lite[2] = 0; a.n_lite[3] = 0; }
-        if (a.n_ptl) { a.n_ptl[0] = 0; a.n_ptl[1] = 0; }
+        if (a.n_ptl) { a.n_ptl[0] = 0; a.n_ptl[1] = 0; a.n_ptl[2] = 0; a.n_ptl[3] = 0; }
         if (a.n_stop) *a.n_stop = 0;
     }
     __syncthreads();
@@ -2179,7 +2179,7 @@ struct Shard {
     // each owner, tails of each owner, the end), heads and tails sent
     std::vector<uint64_t> soff, scnt, lcnt;
     uint32_t pper = BLK;               // k_node_prep / k_desc: nodes per block (a multiple of BLK)
-    uint32_t pgrid = 0, cgrid = 0, rgrid = 0, tgrid = 0, sgrid = 0, lgrid = 0, qgrid = 0;   // stats rows: prepare,
+    uint32_t pgrid = 0, cgrid = 0, rgrid = 0, tgrid = 0, sgrid = 0, lgrid = 0, qgrid = 0, egrid = 0;   // stats rows: prepare,
                                    // consume, relay, plumtree, shuffle-start, lite, Plumtree-lane blocks
     // pinned host words: NST stats and the consume span (stat_out), then the
     // outbox total and the routed record count: the round's two read-backs
@@ -2295,6 +2295,30 @@ namespace {
 // through the owner partition and an exchange
 inline bool local_route(const psim_handle* h) { return h->G == 1 && !h->ranked; }
 
+// PSIM_PTL_EARLY, read once: where the early part of k_ptl's list runs (the
+// nodes whose HyParView phase k_relay finished: RoundArgs::n_ptl).  1: as a
+// block range of k_hv_phase, beside the HyParView bodies, and k_ptl then runs
+// the late part alone; 0: one k_ptl launch of both parts after the phase; 2:
+// a diagnostic -- two k_ptl launches after k_hv_phase, early then late, so a
+// kernel trace shows each part's own time.  Wherever k_hv_phase does not run
+// all its ranges (phase_consume) k_ptl runs both parts in one launch.
+// The default is 0: at 2^20 nodes the overlap measured 10 to 60 us a round
+// slower, wherever the range sat among the block indices
+// (profiles/ptl_early/ab_log.txt) -- the lite range
+// fills every wave slot the fused kernel's 128 VGPRs allow, so the early
+// waves take slots from it, and a k_ptl launch of one part costs a whole
+// chain of dependent loads however short its list (early 71 us + late 49 us
+// alone against 93 us for both).
+constexpr int PTL_EARLY_DEFAULT = 0;
+int ptl_early_knob() {
+    static const int v = [] {
+        const char* e = getenv("PSIM_PTL_EARLY");
+        const int x = e && *e ? atoi(e) : -1;
+        return x >= 0 && x <= 2 ? x : PTL_EARLY_DEFAULT;
+    }();
+    return v;
+}
+
 RoundArgs make_args(psim_handle* h, Shard* s) {
     RoundArgs a;
     memset(&a, 0, sizeof a);
@@ -2325,6 +2349,7 @@ RoundArgs make_args(psim_handle* h, Shard* s) {
     a.start = s->start.p;
     a.pl = c.manager == PSIM_MANAGER_PLUGGABLE;
     a.xbot = c.manager == PSIM_MANAGER_XBOT; a.xbot_period = c.xbot_period;
+    a.ptl_split = ptl_early_knob() != 0;
     a.strategy = c.strategy; a.periodic = c.periodic_interval; a.scamp_c = c.scamp_c;
     a.fanout = c.fanout; a.fw = h->fw; a.tomb = h->tomb;
     a.fbits = s->fbits.p; a.sview = s->sview.p; a.sinv = s->sinv.p;
@@ -2627,7 +2652,11 @@ int phase_events_prepare(psim_handle* h, Shard* s, const RoundCtl& ctl, RoundArg
         s->lgrid = hv ? std::min<uint32_t>((uint32_t)((n + lnodes - 1) / lnodes), h->lite_blocks) : 0;
         const uint32_t qnodes = PTL_BLOCK;
         s->qgrid = hv && h->cfg.plumtree ? std::min<uint32_t>((uint32_t)((n + qnodes - 1) / qnodes), h->ptl_blocks) : 0;
-        TRY(s->stat_part.ensure((size_t)(s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid) *
+        // (the early part of k_ptl's list where it runs on its own: a grid
+        // and stats rows like k_ptl's -- a launch of both parts zeroes them,
+        // row for row)
+        s->egrid = ptl_early_knob() ? s->qgrid : 0;
+        TRY(s->stat_part.ensure((size_t)(s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid + s->egrid) *
                                 NST));
         k_node_prep<<<s->pgrid, BLK, 0, s->stream>>>(a, s->bmask.p, s->bound.p, s->stat_part.p, s->ocnt.p,
                                                      s->btot.p, s->pper, s->pscan.p, s->gcnt.p, (uint32_t)s->gcnt.n);
@@ -2703,6 +2732,7 @@ args:
     a.stat_shuf = s->stat_part.p + (size_t)(s->pgrid + s->cgrid + s->rgrid + s->tgrid) * NST;
     a.stat_lite = s->stat_part.p + (size_t)(s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid) * NST;
     a.stat_ptl = s->stat_part.p + (size_t)(s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid) * NST;
+    a.stat_ptle = s->egrid ? a.stat_ptl + (size_t)s->qgrid * NST : nullptr;
     return PSIM_OK;
 }
 
@@ -2775,9 +2805,16 @@ int phase_consume(psim_handle* h, Shard* s, RoundArgs& a) {
             return v == 2 || v == 3 ? v : 0;
         }();
         const bool fused = fused_env && !a.crash_round && !serial_env && !conc_env && h->lite.kernel == k_lite_quarter;
+        // The early part of k_ptl's list (k_relay's bins: nodes whose
+        // HyParView phase its lane finished) depends on none of these
+        // kernels: with all the ranges in one launch it is k_hv_phase's
+        // fourth (PSIM_PTL_EARLY, ptl_early_knob), and k_ptl runs the late
+        // part; on every other path k_ptl runs both after the phase
+        const int early = fused && fused_env == 3 && s->egrid ? ptl_early_knob() : 0;
         if (fused) {
-            const uint32_t lg = fused_env == 3 ? s->lgrid : 0;
-            if (s->sgrid + s->cgrid + lg) k_hv_phase<<<s->sgrid + s->cgrid + lg, BLK, 0, s->stream>>>(a, s->sgrid, s->cgrid);
+            const uint32_t lg = fused_env == 3 ? s->lgrid : 0, eg = early == 1 ? s->egrid : 0;
+            if (s->sgrid + s->cgrid + lg + eg)
+                k_hv_phase<<<s->sgrid + s->cgrid + lg + eg, BLK, 0, s->stream>>>(a, s->sgrid, s->cgrid, eg);
             if (fused_env == 2) launch_lite(h, s, a, s->stream);
         } else if (serial) {
             k_shuf<<<s->sgrid, BLK, 0, s->stream>>>(a);
@@ -2796,7 +2833,9 @@ int phase_consume(psim_handle* h, Shard* s, RoundArgs& a) {
             }
         }
         if (s->qgrid) {
-            k_ptl<<<s->qgrid, PTL_BLOCK, 0, s->stream>>>(a);
+            if (early == 2) k_ptl_part<<<s->egrid, PTL_BLOCK, 0, s->stream>>>(a, PTL_EARLY);
+            if (early) k_ptl_part<<<s->qgrid, PTL_BLOCK, 0, s->stream>>>(a, PTL_LATE);
+            else k_ptl<<<s->qgrid, PTL_BLOCK, 0, s->stream>>>(a);
         }
         if (s->tgrid) {
             RoundArgs c = a;
@@ -2857,7 +2896,7 @@ int route_group(psim_handle* h, Shard* s, bool dense, uint32_t m, bool fixed = f
     const uint32_t lcap = lidx_ok && W == (1u << WSHIFT_MIN) ? ROUTE_LIDX : 0u;
     const size_t lds_h = (size_t)nb * 4, lds_r = (size_t)W * 16 + (size_t)lcap * 4;
     // the round's stats rows (every node-phase kernel's blocks) are complete
-    const uint32_t rows = s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid;
+    const uint32_t rows = s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid + s->egrid;
     // (a batched rank round, fixed: the stats came summed in the message
     // headers -- k_bucket_hist's block 0 adds them up, no tiles here)
     const StatsIn st{s->stat_part.p, rows,
@@ -2967,7 +3006,7 @@ int phase_partition(psim_handle* h, Shard* s, bool fixed = false) {
     // message headers by k_owner_offsets (the route sums the received ones)
     StatsIn st{};
     if (fixed) {
-        const uint32_t rows = s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid;
+        const uint32_t rows = s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid + s->egrid;
         st = StatsIn{s->stat_part.p, rows,
                      std::min<uint32_t>(nblk, std::min<uint32_t>(STAT_TILES, std::max<uint32_t>(1, rows / 32))),
                      s->stat_tile.p, s->stat_out.p, s->pin_dev + (size_t)s->stat_slot * PIN_STRIDE,
@@ -3298,7 +3337,7 @@ int run_round(psim_handle* h, uint64_t* st, bool events_applied = false, bool fr
                          "%u to k_shuf, %u to k_consume_lite, %u to k_ptl, outbox bound %llu, emitted %llu\n",
                          (unsigned long long)h->round, s->idx, read1(s, s->d_nact.p), read1(s, s->n_slow.p),
                          read1(s, s->n_pt.p), read1(s, s->n_shuf.p), read1(s, s->n_lite.p) + read1(s, s->n_lite.p + 1) + read1(s, s->n_lite.p + 2) + read1(s, s->n_lite.p + 3),
-                         read1(s, s->n_ptl.p) + read1(s, s->n_ptl.p + 1),
+                         read1(s, s->n_ptl.p) + read1(s, s->n_ptl.p + 1) + read1(s, s->n_ptl.p + 2) + read1(s, s->n_ptl.p + 3),
                          (unsigned long long)s->pin[PIN_TOTAL], (unsigned long long)em);
         }
         if (s->pin[NST] != ~0ull && s->pin[NST + 1] > s->pin[NST]) {   // 100 MHz ticks
@@ -3756,7 +3795,7 @@ int shard_alloc(psim_handle* h, Shard* s) {
     rc |= s->desc_pt.alloc(n); rc |= s->n_pt.alloc(1);
     rc |= s->desc_shuf.alloc(n); rc |= s->n_shuf.alloc(1);
     rc |= s->desc_lite.alloc(2 * n); rc |= s->n_lite.alloc(4);
-    rc |= s->desc_ptl.alloc(n); rc |= s->n_ptl.alloc(2);
+    rc |= s->desc_ptl.alloc(2 * n); rc |= s->n_ptl.alloc(4);
     if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE) { rc |= s->stop_ids.alloc(n); rc |= s->n_stop.alloc(1); }
     rc |= s->stat_out.alloc(STAT_OUT_N);   // + the consume span, the rank path's x-words
     rc |= s->ctl.alloc(4);   // (the abort word: code, round; then the fused route's overflow flag)
@@ -4915,22 +4954,25 @@ int psim_kernel_times(psim_handle* h, const char** names, double* ms, uint64_t* 
 // k_pt: out[4 k] nodes processed (stats nodes_processed), out[4 k + 1]
 // records delivered, out[4 k + 2] records emitted, out[4 k + 3] 0; with cap
 // >= 28 then k_node_prep's quiet lazy ticks (nodes processed without a
-// kernel).  Returns the number of entries (6 or 7); 0 for the pluggable
-// manager's one kernel.
+// kernel); with cap >= 32 then the early part of k_ptl's list where it ran on
+// its own (k_hv_phase's range, or PSIM_PTL_EARLY=2's launch; zeros where one
+// k_ptl launch ran both parts) -- the k_ptl entry is the sum of both parts
+// either way.  Returns the number of entries (6, 7 or 8); 0 for the
+// pluggable manager's one kernel.
 int psim_debug_kernel_counts(psim_handle* h, uint64_t* out, int cap) {
     if (!h || !out || cap < 24) return PSIM_EINVAL;
     if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE) return 0;
     Shard* s = h->shards[0];
-    const uint32_t rows = s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid;
+    const uint32_t rows = s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid + s->egrid;
     std::vector<uint64_t> st((size_t)rows * NST);
     HIP_TRY(hipStreamSynchronize(s->stream));
     HIP_TRY(hipMemcpy(st.data(), s->stat_part.p, st.size() * 8, hipMemcpyDeviceToHost));
-    // row ranges (make_args: prepare, consume, relay, pt, shuf, lite, ptl)
+    // row ranges (make_args: prepare, consume, relay, pt, shuf, lite, ptl, ptl early)
     const uint32_t b_cons = s->pgrid, b_rel = b_cons + s->cgrid, b_pt = b_rel + s->rgrid, b_sh = b_pt + s->tgrid,
-                   b_li = b_sh + s->sgrid, b_pl = b_li + s->lgrid, b_end = b_pl + s->qgrid;
-    const uint32_t rng[7][2] = {{b_rel, b_pt}, {b_sh, b_li}, {b_li, b_pl}, {b_cons, b_rel}, {b_pl, b_end}, {b_pt, b_sh},
-                                {0, b_cons}};
-    const int nk = cap >= 28 ? 7 : 6;
+                   b_li = b_sh + s->sgrid, b_pl = b_li + s->lgrid, b_ple = b_pl + s->qgrid, b_end = b_ple + s->egrid;
+    const uint32_t rng[8][2] = {{b_rel, b_pt}, {b_sh, b_li}, {b_li, b_pl}, {b_cons, b_rel}, {b_pl, b_end}, {b_pt, b_sh},
+                                {0, b_cons}, {b_ple, b_end}};
+    const int nk = cap >= 32 ? 8 : cap >= 28 ? 7 : 6;
     for (int k = 0; k < nk; k++) {
         uint64_t v[3] = {0, 0, 0};
         for (uint32_t r = rng[k][0]; r < rng[k][1]; r++) {

@@ -28,6 +28,7 @@ struct RoundArgs {
     uint32_t max_active, min_active, max_passive, arwl, prwl, k_active, k_passive;
     uint32_t shuffle_period, promotion_period, random_promotion, plumtree, lazy_tick_period;
     uint32_t xbot, xbot_period;   // X-BOT manager (PSIM_MANAGER_XBOT) and its xbot_execution period
+    uint32_t ptl_split;           // k_relay files k_ptl's nodes by dependency (n_ptl; PSIM_PTL_EARLY != 0)
     // per-round scalars
     uint32_t crash_round, tracked_msg;
     uint32_t upart_dirty;       // this round's events changed F_UP or a partition: k_node_prep rebuilds upart
@@ -94,9 +95,18 @@ struct RoundArgs {
                                 // half's front and back, [2] and [3] from the second's
     uint64_t* stat_lite;        // the lite kernel's per-block stats rows
     uint4* desc_ptl;            // ... and the nodes with Plumtree work and no origin, for k_ptl:
-    uint32_t* n_ptl;            // [0] from the front, those with a BROADCAST in their inbox, [1] from
-                                // the back (desc_ptl[n_local - 1 - i]), the others (ptl_desc)
+    uint32_t* n_ptl;            // 2 n_local slots, four bins laid out as the lite list's: the early
+                                // part (nodes whose HyParView phase k_relay itself finished) in the
+                                // first half, [0] from its front, those with a BROADCAST in their
+                                // inbox, [1] from its back, the others; the late part (heavy, lite
+                                // and k_shuf nodes) in the second half, [2] and [3] (ptl_desc).
+                                // Without ptl_split every node is filed as early: one list in
+                                // node order, which a launch of both parts reads with more of
+                                // each line (config E at 2^26: k_ptl 4.5 % faster than over the
+                                // split list, profiles/ptl_early/ab_log.txt)
     uint64_t* stat_ptl;         // k_ptl's per-block stats rows
+    uint64_t* stat_ptle;        // ... and those of the early part where it runs as a launch or a
+                                // block range of its own (phase_consume; nullptr: never)
     uint64_t* stat_relay;
     uint64_t* stat_pt;          // k_pt's per-block stats rows
     const Msg* rec_in;          // dense, in inbox order (node runs at in_beg)
@@ -165,10 +175,11 @@ __global__ void k_shuf(RoundArgs args);
 __global__ void k_consume_lite(RoundArgs args);
 __global__ void k_lite_half(RoundArgs args);
 __global__ void k_lite_quarter(RoundArgs args);
-// k_shuf's, k_consume's and k_lite_quarter's bodies on the block ranges
-// [0, sgrid), [sgrid, sgrid + cgrid) and the rest (psim_consume.hip); `args`
-// is the round's (k_relay's), with k_consume's list in desc_slow / n_slow
-__global__ void k_hv_phase(RoundArgs args, uint32_t sgrid, uint32_t cgrid);
+// k_shuf's, k_consume's and k_lite_quarter's bodies and the early part of
+// k_ptl's list on the block ranges [0, sgrid), [sgrid, sgrid + cgrid), the
+// lite blocks, then the last egrid (psim_consume.hip); `args` is the round's
+// (k_relay's), with k_consume's list in desc_slow / n_slow
+__global__ void k_hv_phase(RoundArgs args, uint32_t sgrid, uint32_t cgrid, uint32_t egrid);
 struct LiteKernel {
     void (*kernel)(RoundArgs);
     uint32_t block;             // threads per block
@@ -178,8 +189,11 @@ struct LiteKernel {
 };
 LiteKernel lite_kernel_groups(bool half);   // k_lite_quarter / k_lite_half (psim_lite.hip)
 LiteKernel lite_kernel_wave();              // k_consume_lite (psim_consume.hip)
-// lane-per-node Plumtree phases (psim_consume.hip); hands k_pt what does not fit
-__global__ void k_ptl(RoundArgs args);
+// lane-per-node Plumtree phases (psim_consume.hip); hands k_pt what does not fit.
+// `part`: which of k_relay's two parts of the list the launch runs
+enum : uint32_t { PTL_BOTH = 0, PTL_EARLY = 1, PTL_LATE = 2 };
+__global__ void k_ptl(RoundArgs args);                       // both parts, in list order
+__global__ void k_ptl_part(RoundArgs args, uint32_t part);   // PTL_EARLY or PTL_LATE
 // the Plumtree phase of the nodes k_relay listed (psim_consume.hip)
 __global__ void k_pt(RoundArgs args);
 // diagnostic builds (-DPSIM_STAMPS): per-phase cycle sums of k_consume, reset on read
@@ -212,13 +226,27 @@ __device__ __forceinline__ bool crashed_now(Args& a, uint32_t id) {
 
 typedef const __attribute__((address_space(4))) RoundArgs KArgs;
 
-// entry i of k_ptl's list: the BROADCAST nodes k_relay put at the front, then
-// the others it put at the back -- so a wave's lanes mostly run the same
-// handlers (a first delivery's eager push and lazy adds, or the light IHAVE
-// answers, acks and lazy ticks), not the union of both
+// entry i of a part of k_ptl's list (c: n_ptl's four counts): the BROADCAST
+// nodes k_relay put at the front of the part's half, then the others it put
+// at the half's back -- so a wave's lanes mostly run the same handlers (a
+// first delivery's eager push and lazy adds, or the light IHAVE answers, acks
+// and lazy ticks), not the union of both; PTL_BOTH: the early part, then the
+// late one
+// (c: n_ptl's four counts with the other part's zeroed, ptl_counts; the
+// layout is the lite list's, lite_at below)
 template <class Args>
-__device__ __forceinline__ uint4 ptl_desc(Args& a, uint32_t n0, uint32_t i) {
-    return a.desc_ptl[i < n0 ? i : a.n_local - 1 - (i - n0)];
+__device__ __forceinline__ uint4 ptl_desc(Args& a, const uint32_t (&c)[4], uint32_t i) {
+    const uint32_t n = a.n_local;
+    return a.desc_ptl[i < c[0] ? i
+                    : i < c[0] + c[1] ? n - 1 - (i - c[0])
+                    : i < c[0] + c[1] + c[2] ? n + (i - c[0] - c[1])
+                    : 2 * n - 1 - (i - c[0] - c[1] - c[2])];
+}
+template <class Args>
+__device__ __forceinline__ void ptl_counts(Args& a, uint32_t part, uint32_t (&c)[4], uint32_t& nq) {
+    c[0] = part != PTL_LATE ? a.n_ptl[0] : 0u; c[1] = part != PTL_LATE ? a.n_ptl[1] : 0u;
+    c[2] = part != PTL_EARLY ? a.n_ptl[2] : 0u; c[3] = part != PTL_EARLY ? a.n_ptl[3] : 0u;
+    nq = c[0] + c[1] + c[2] + c[3];
 }
 // entry i of the lite list, in four bins k_relay fills: nodes with a SHUFFLE
 // terminal (a sublist of the passive view, a reply and a merge) and nothing
@@ -263,7 +291,7 @@ constexpr uint32_t layout_sig() {
     const uint64_t v[] = {
         PSIM_ABI_VERSION, sizeof(RoundArgs), offsetof(RoundArgs, flags), offsetof(RoundArgs, upart),
         offsetof(RoundArgs, hdr), offsetof(RoundArgs, conn), offsetof(RoundArgs, outx_rows),
-        offsetof(RoundArgs, desc), offsetof(RoundArgs, desc_lite), offsetof(RoundArgs, stat_pt),
+        offsetof(RoundArgs, desc), offsetof(RoundArgs, desc_lite), offsetof(RoundArgs, stat_ptle), offsetof(RoundArgs, stat_pt),
         offsetof(RoundArgs, rec_out), offsetof(RoundArgs, okey), offsetof(RoundArgs, ktime),
         offsetof(RoundArgs, ctl), offsetof(RoundArgs, fbits), offsetof(RoundArgs, omit),
         sizeof(Hdr), sizeof(Msg), sizeof(upart_t), PSIM_SHORT_TAIL, PTL_BLOCK, KEY_DST_BITS, KEY_BCAST,

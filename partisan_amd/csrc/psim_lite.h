@@ -844,10 +844,20 @@ DEV void writeback(Node<W>& x, Lds<W>& w, Cnt& c) {
 }
 
 // ------------------------------------------------------- the kernel body --
+// the block's LDS, in words from a 16-byte aligned base: the stats, then per
+// group STAGE records of 16 words, STAGE route keys and SCR words of scratch
+// (the caller carves: the kernel's own array, or k_hv_phase's, which the
+// bodies of its block ranges share -- static arrays of inlined bodies add up)
+template <uint32_t W>
+struct Carve {
+    using G = Grp<W>;
+    static constexpr uint32_t SREC = (NST * 2 + 3) & ~3u, SKEY = SREC + G::WPB * G::N * G::STAGE * 16,
+                              SCR = SKEY + G::WPB * G::N * G::STAGE, WORDS = SCR + G::WPB * G::N * G::SCR;
+};
 // Block `bid` of `nblk`: the launch's own index and grid in k_lite_quarter /
 // k_lite_half, the lite range's in k_hv_phase (psim_consume.hip).
 template <uint32_t W>
-DEV void lite_kernel(const uint32_t bid, const uint32_t nblk) {
+DEV void lite_kernel(const uint32_t bid, const uint32_t nblk, uint32_t* const pool) {
     using G = Grp<W>;
     constexpr uint32_t WPB = G::WPB, STAGE = G::STAGE;
     // the LDS carve of a wave: per group STAGE records of 16 words, STAGE
@@ -862,10 +872,10 @@ DEV void lite_kernel(const uint32_t bid, const uint32_t nblk) {
     static_assert(WPB * G::N * (STAGE * 16 + STAGE + G::SCR) * 4 + NST * 8 <= 64 * 1024,
                   "the block's LDS: four blocks of it per CU at 4 waves/SIMD");
     if (*kargs().ctl) return;                         // an aborted batch (run_batch)
-    __shared__ unsigned long long sst[NST];
-    __shared__ __attribute__((aligned(16))) uint32_t srecs[WPB][G::N * STAGE * 16];
-    __shared__ uint32_t skeys[WPB][G::N * STAGE];
-    __shared__ uint32_t scrs[WPB][G::N * G::SCR];
+    unsigned long long* const sst = reinterpret_cast<unsigned long long*>(pool);
+    uint32_t* const srecs = pool + Carve<W>::SREC;
+    uint32_t* const skeys = pool + Carve<W>::SKEY;
+    uint32_t* const scrs = pool + Carve<W>::SCR;
 #ifdef PSIM_STAMPS
     __shared__ unsigned long long stls[WPB][32];
     for (int i = threadIdx.x; i < (int)(WPB * 32); i += blockDim.x) (&stls[0][0])[i] = 0;
@@ -875,9 +885,9 @@ DEV void lite_kernel(const uint32_t bid, const uint32_t nblk) {
     const uint32_t wid = threadIdx.x >> 6, g = G::idx();
     Lds<W> w;
     w.sst = sst;
-    w.srec = srecs[wid] + g * (STAGE * 16);
-    w.skey = skeys[wid] + g * STAGE;
-    w.scr = scrs[wid] + g * G::SCR;
+    w.srec = srecs + (wid * G::N + g) * (STAGE * 16);
+    w.skey = skeys + (wid * G::N + g) * STAGE;
+    w.scr = scrs + (wid * G::N + g) * G::SCR;
     w.KM = G::magic_lanes();
 #ifdef PSIM_STAMPS
     w.stl = stls[wid];

@@ -10,10 +10,12 @@ using namespace lite;
 // (two entry points: the launch bounds differ, and profilers and
 // psim_kernel_times name them)
 __global__ void __launch_bounds__(64 * PSIM_HALF_WPB, PSIM_HALF_WAVES) k_lite_half(RoundArgs args) {
-    lite_kernel<32>(blockIdx.x, gridDim.x);
+    __shared__ __attribute__((aligned(16))) uint32_t pool[Carve<32>::WORDS];
+    lite_kernel<32>(blockIdx.x, gridDim.x, pool);
 }
 __global__ void __launch_bounds__(64 * PSIM_QUARTER_WPB, PSIM_QUARTER_WAVES) k_lite_quarter(RoundArgs args) {
-    lite_kernel<16>(blockIdx.x, gridDim.x);
+    __shared__ __attribute__((aligned(16))) uint32_t pool[Carve<16>::WORDS];
+    lite_kernel<16>(blockIdx.x, gridDim.x, pool);
 }
 
 // k_lite_quarter's grid is a row per local node, capped (psim_create); the
