@@ -8,7 +8,9 @@
 // round and shard (DESIGN.md sections 3 and 7):
 //   events   k_crash / k_join / k_bcast_reset    (same event list on every shard)
 //   prepare  k_node_prep (packed bound | work flag per node), one scan of them,
-//            k_desc (outbox bases + descriptors of the nodes with work)
+//            k_desc (outbox bases + descriptors of the nodes with work); inside a
+//            batch the route of the round before does k_node_prep's part
+//            (RoutePrep, PSIM_PREP_FUSED)
 //   consume  k_consume (psim_consume.hip)
 //   route    G == 1: count (atomics) -> scan -> scatter -> per-run sort of
 //                    source indices -> gather (stable radix sort when one run
@@ -583,7 +585,7 @@ __global__ void __launch_bounds__(RB_STEP) k_bucket_scatter(RouteIn in, uint32_t
 // `fused`): k_bucket_hist, k_bucket_offsets and k_bucket_scatter in one
 // launch.  Each block counts its records per bucket in LDS, reserves its
 // share of every bucket it touches with one global atomic per bucket
-// (gcnt, zeroed by k_node_prep), and scatters its pairs into the bucket's
+// (gcnt, zeroed by k_node_prep or, on a round the route prepared, k_desc), and scatters its pairs into the bucket's
 // fixed region [b capb, (b + 1) capb) of `pairs`.  The order of a bucket's
 // pairs then depends on the atomics' timing -- which k_bucket_route never
 // relied on: it ranks each destination's records by LDS atomics and sorts
@@ -977,16 +979,248 @@ __device__ __forceinline__ uint4 rec_piece(const Msg* __restrict__ rec, uint32_t
     return p < 2 || wire_long(tt) ? v : make_uint4(0, 0, 0, 0);
 }
 
+constexpr uint64_t NODE_STATE_BYTES = 416;   // SURVEY 8(d): HyParView 304 + Plumtree 112 per node
+
+__device__ __forceinline__ bool due(uint32_t period, uint32_t r, uint32_t start) {
+    return period > 0 && r > start && ((r - start) % period) == 0;
+}
+
+#ifdef PSIM_BOUND_TERMS
+// diagnostic build (make evariant V=bterms X=-DPSIM_BOUND_TERMS): the outbox
+// bound's terms summed over the nodes of every round since psim_step last
+// printed them (PSIM_TRACE_BOUND)
+enum { BT_RESP, BT_TIMER, BT_PUSH, BT_PUSH_NE, BT_NPUSH, BT_LAZY, BT_ON, BT_NL, BT_LC, BT_CRASH, BT_XBOT,
+       BT_BUMP, BT_TOTAL, BT_C, BT_QUIET, BT_ROUNDS, BT_N };
+__device__ unsigned long long g_bterm[BT_N];
+#define BTERM(k, v) (bt[k] += (v))
+#define BT_PARAM , unsigned long long* bt
+#define BT_ARG , bt
+#else
+#define BTERM(k, v) ((void)0)
+#define BT_PARAM
+#define BT_ARG
+#endif
+
+// the prepare's sums over a thread's nodes: live nodes, messages addressed to
+// dead ones, the bounds, the work flags, the quiet lazy ticks (nodes, failed
+// sends)
+struct PrepSums {
+    unsigned long long up, drop, bs, ws, qp, qf;
+};
+
+// One HyParView / X-BOT node's packed (bound << 32 | work) word of the
+// prepare, from its inputs -- the flag byte, the inbox count | bound sum << 32
+// (cbi), the BROADCAST slot mask, the start round, the origin word -- and its
+// terms added to `s`.  `a`: the round's scalars and rows (RoundArgs in
+// k_node_prep; RoutePrep in the route, whose rounds have no events: EVENTS =
+// false leaves out the crash-round scan and the lazy wake).  No stores.
+template <bool EVENTS, class A>
+__device__ __forceinline__ uint64_t hv_node_prep(const A& a, uint32_t i, uint8_t f, unsigned long long cbi,
+                                                 unsigned long long bm_, uint32_t st, uint32_t org_,
+                                                 PrepSums& s BT_PARAM) {
+    uint64_t b = 0;
+    uint32_t w = 0;
+    const uint32_t c = (uint32_t)cbi;
+    if (f & F_UP) {
+        const uint32_t r = a.round;
+        bool origin = org_ != 0;
+        const Hdr& x = a.hdr[i];      // (read only where needed: a fresh start, a full nibble)
+        // the due timers' sends: the JOIN of a fresh start, a
+        // promotion's NEIGHBOR_REQUEST (the active view may shrink
+        // during the round: any due promotion), a shuffle
+        const bool promo = a.random_promotion && due(a.promotion_period, r, st);
+        b = (cbi >> 32) + (st == r && x.join_contact != PSIM_NONE ? 1u : 0u) + (promo ? 1u : 0u) +
+            (due(a.shuffle_period, r, st) ? 1u : 0u);
+        BTERM(BT_RESP, cbi >> 32);
+        BTERM(BT_TIMER, b - (cbi >> 32));
+        // per BROADCAST message slot a first delivery's eager push
+        // and lazy adds (plus the origin's): at most the root's sets
+        // at round start -- or the common eagers of a new root or of a
+        // reset -- plus one per message handled before; the push's
+        // sends need an active connection: at most two per active
+        // member (its atom and its node_spec identity, App. A Q6)
+        // (round 6: a slot's pushes and lazy adds together are at most
+        // the root's eager and lazy sets at round start -- or the
+        // common eagers of a new root or a reset -- plus one per
+        // message handled before: update_peers/5 (pt:593-609) adds one
+        // peer a message to their union, and the pushes go to the
+        // eager set, the adds to the lazy one (pt:374-378))
+        const unsigned long long bm = c ? bm_ : 0ull;
+        const uint32_t pushes = (uint32_t)__popcll(bm) + (origin ? 1u : 0u);
+        const bool lazy = a.plumtree && due(a.lazy_tick_period, r, st);
+        uint32_t lazy_add = 0, push_sum = 0, union_sum = 0;
+        if (pushes) {
+            const uint4 r0 = *reinterpret_cast<const uint4*>(a.pt_rt + (size_t)i * RT_WORDS);
+            const uint2 cn = *reinterpret_cast<const uint2*>(a.pt_rt + (size_t)i * RT_WORDS + RT_EN);
+            const uint32_t rts[4] = {r0.x, r0.y, r0.z, r0.w};
+            auto push = [&](uint32_t root) {
+                uint32_t ne = PSIM_PT_MEMBERS_CAP, nl = 0, ne0 = 0;
+#pragma unroll
+                for (int k = 0; k < PSIM_PT_ROOTS; k++)
+                    if (rts[k] == root) {
+                        ne0 = (cn.x >> (8 * k)) & 0xFFu;
+                        ne = max(ne, ne0);
+                        nl = (cn.y >> (8 * k)) & 0xFFu;
+                    }
+                const uint32_t pb = min(2u * PSIM_ACTIVE_CAP, ne + c);
+                push_sum += pb;
+                lazy_add += nl + c;
+                union_sum += min(pb + nl + c, max((uint32_t)PSIM_PT_MEMBERS_CAP, ne0 + nl) + c);
+                BTERM(BT_PUSH, min(2u * PSIM_ACTIVE_CAP, ne + c));
+                BTERM(BT_PUSH_NE, min(2u * PSIM_ACTIVE_CAP, ne));
+                BTERM(BT_NPUSH, 1);
+                BTERM(BT_NL, nl);
+                BTERM(BT_LC, c);
+            };
+            for (unsigned long long m = bm; m; m &= m - 1) push(a.slots[PSIM_MSG_SLOTS + __ffsll(m) - 1]);
+            if (origin) push((a.lo + i) | PSIM_MAP_BIT);
+        }
+        // a due lazy tick sends every outstanding entry: those left
+        // from last round and those this round's pushes add, at most
+        // PT_OUT_CAP
+        // (the flag byte's nibble is min(out_n, 15) after the node's
+        // last round: the header only when it saturates)
+        // (with the tick: the pushes P and the tick's IHAVEs, at most
+        // min(PT_OUT_CAP, on + L), where P + L is at most the slots'
+        // union term)
+        if (lazy) {
+            const uint32_t fo = (uint32_t)f >> F_OUTN_SHIFT;
+            const uint32_t on = fo < 15 ? fo : (uint32_t)x.out_n;
+            const uint32_t pl = min(push_sum + min((uint32_t)PSIM_PT_OUT_CAP, on + lazy_add), on + union_sum);
+            b += pl;
+            BTERM(BT_LAZY, pl - push_sum);
+            BTERM(BT_ON, on);
+        } else {
+            b += push_sum;
+        }
+        if (pushes) BTERM(BT_C, c);
+        // a crash round: a NEIGHBOR_REQUEST per crashed active member
+        // (bounded over every crashed member); EXIT work for a
+        // crashed member held over a connection -- an active member
+        // not marked PSIM_CONN_DOWN, or a lingering peer (App. A Q11)
+        bool exits = false;
+        bool lazy_wake = false;
+        if constexpr (EVENTS) {
+            lazy_wake = a.lazy_wake;
+            if (a.crash_round) {
+                const uint4* ar = reinterpret_cast<const uint4*>(a.act + (size_t)i * PSIM_ACTIVE_CAP);
+                const uint4 a0 = ar[0], a1 = ar[1];
+                const uint32_t av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                uint32_t cv[PSIM_CONN_CAP] = {};
+                const uint32_t cn = x.conn_n;
+                if (cn) {
+                    const uint4* cr = reinterpret_cast<const uint4*>(a.conn + (size_t)i * PSIM_CONN_CAP);
+                    const uint4 c0 = cr[0], c1 = cr[1];
+                    cv[0] = c0.x; cv[1] = c0.y; cv[2] = c0.z; cv[3] = c0.w;
+                    cv[4] = c1.x; cv[5] = c1.y; cv[6] = c1.z; cv[7] = c1.w;
+                }
+#pragma unroll
+                for (int k = 0; k < PSIM_ACTIVE_CAP; k++)
+                    if ((uint32_t)k < x.act_n && av[k] < a.n_nodes && av[k] != a.lo + i &&
+                        crashed_now(a, av[k])) {
+                        b++;
+                        BTERM(BT_CRASH, 1);
+                        bool down = false;
+#pragma unroll
+                        for (int j = 0; j < PSIM_CONN_CAP; j++) down |= (uint32_t)j < cn && cv[j] == (av[k] | PSIM_CONN_DOWN);
+                        exits |= !down;
+                    }
+#pragma unroll
+                for (int j = 0; j < PSIM_CONN_CAP; j++)
+                    exits |= (uint32_t)j < cn && !(cv[j] & PSIM_CONN_DOWN) && crashed_now(a, cv[j] & KEY_DST_MASK);
+            }
+        }
+        // a quiet node (entries outstanding, F_LAZY clear: its last
+        // tick reached no peer) runs only for other work: its tick
+        // fails every entry again (pt:443-453 over send/3), counted
+        // here -- the node processed, a failed send per entry.  Only
+        // with a tick every round (else a round without one could
+        // connect a peer unseen) and no waking event
+        const uint32_t fon = (uint32_t)f >> F_OUTN_SHIFT;
+        const bool quiet_ok = a.lazy_tick_period == 1 && !lazy_wake && !(f & F_LAZY);
+        w = c > 0 || st == r || exits || (fon && !quiet_ok) || origin ||
+            (a.random_promotion && (f & F_LOWACT) && due(a.promotion_period, r, st)) ||
+            due(a.shuffle_period, r, st);
+        if (a.xbot) {
+            // X-BOT: a due xbot_execution sends to two candidates at
+            // most; the 'EXIT' of each connection pid stopped last
+            // round may promote (a NEIGHBOR_REQUEST each)
+            const bool xb = due(a.xbot_period, r, st);
+            const uint32_t cl = x.conn_cl;
+            b += (xb ? 2u : 0u) + cl;
+            BTERM(BT_XBOT, (xb ? 2u : 0u) + cl);
+            w = w || xb || cl;
+        }
+        // a working node's first slot is reserved: a wave that emits
+        // nothing rewrites it (flush_recs' fixed store)
+        if (w && b == 0) { b = 1; BTERM(BT_BUMP, 1); }
+        if (!w && fon && lazy) {
+            s.qp++;
+            s.qf += fon < 15 ? fon : (uint32_t)x.out_n;
+            BTERM(BT_QUIET, 1);
+            b = 0;
+        }
+        s.up++;
+    } else {
+        s.drop += c;
+    }
+    s.bs += b;
+    s.ws += w;
+    BTERM(BT_TOTAL, b);
+    // one scan gives both the outbox base (high word: the bounds) and
+    // the position in the active list (low word: the work flags)
+    return (b << 32) | w;
+}
+
+// The prepare of round `round` done by the route of the round before
+// (k_bucket_route<false>, the fused local route of a batch: run_batch), whose
+// blocks hold each node's inbox count, bound sum and BROADCAST mask in LDS:
+// what k_node_prep would store for a round without events -- the packed words,
+// ocnt = 0, the ranges' sums for k_desc (tiles, btot) and the ranges' stats
+// rows.  A range is 2^pshift nodes, at most a bucket.  packed == nullptr: off.
+struct RoutePrep {
+    uint32_t round, n_nodes, lo;
+    uint32_t shuffle_period, promotion_period, random_promotion, plumtree, lazy_tick_period, xbot, xbot_period;
+    uint32_t pshift, nranges;
+    const uint8_t* flags;
+    const Hdr* hdr;
+    const uint32_t *pt_rt, *slots, *start;
+    uint64_t* packed;
+    uint32_t* ocnt;
+    uint64_t* tiles;
+    unsigned long long* btot;
+    uint64_t* part;
+};
+constexpr uint32_t RP_NODES = (1u << WSHIFT_MIN) / RR_THREADS;   // nodes a thread whose flag and start words load early
+static_assert(RP_NODES == 2, "k_bucket_route's prepare holds the first two nodes' words");
+constexpr uint32_t RP_RANGES = (1u << WSHIFT_MAX) / BLK;          // ranges a bucket at most
+enum { RP_BLO, RP_BHI, RP_UP, RP_W, RP_QP, RP_DROP, RP_QF, RP_N = 8 };   // a range's sums in LDS (the bound: 64 bits)
+static_assert((1u << WSHIFT_MIN) * 16 + ROUTE_LIDX * 4 + (PSIM_RR_THREADS + 4) * 4 + RP_RANGES * RP_N * 4 + 256 <= 80 * 1024,
+              "k_bucket_route at W = 2^11 with the prepare's range sums: two blocks a CU");
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// ... of a term that is zero in every lane of most waves (uniform branch)
+__device__ __forceinline__ uint32_t wave_sum_rare(uint32_t v) { return __ballot(v != 0) ? wave_sum(v) : 0u; }
+
 // One block per bucket of W destinations; LDS holds per destination the
 // count, the bound sum (later the run start, in the same words) and the
 // BROADCAST message-slot mask (64 bits): 4 x W words.
-template <bool WIRE>
-__global__ void __launch_bounds__(RR_THREADS) k_bucket_route(
+// PREP: the launch prepares the next round (rp; the fused local route only).
+// (8 waves a SIMD: two blocks a CU -- the next round's prepare would take the
+// kernel to 89 VGPRs and one block without the bound; every other launch runs
+// the instantiation without it, 50 VGPRs)
+template <bool WIRE, bool PREP = false>
+__global__ void __launch_bounds__(RR_THREADS, 8) k_bucket_route(
     uint32_t n, uint32_t wshift, uint32_t regcap, const uint32_t* __restrict__ base,
     const uint2* __restrict__ pairs, const Msg* __restrict__ rec, const Wire* __restrict__ heads,
     const Wire* __restrict__ tails, uint32_t* rank, unsigned long long* cb,
     unsigned long long* bmask, uint32_t* in_beg, uint32_t* idx, uint32_t* tmp, Msg* __restrict__ inbox, uint64_t* hm,
-    uint64_t cap, uint32_t* ctl, const uint32_t* gcnt, uint32_t capb, uint32_t round1, StatsIn st, uint32_t lcap) {
+    uint64_t cap, uint32_t* ctl, const uint32_t* gcnt, uint32_t capb, uint32_t round1, StatsIn st, uint32_t lcap,
+    RoutePrep rp) {
     if (*ctl) return;                                 // an aborted batch (run_batch)
     // (the dynamic words hold 64-bit masks: 8-byte aligned -- a 4-byte static
     // word in front of them misaligned ds_or_b64 and faulted; the long-run
@@ -994,6 +1228,7 @@ __global__ void __launch_bounds__(RR_THREADS) k_bucket_route(
     extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
     __shared__ __attribute__((aligned(16))) uint32_t spart[RR_THREADS + 4];
     uint32_t& s_nl = spart[RR_THREADS];
+    __shared__ __attribute__((aligned(8))) uint32_t s_rp[RP_RANGES][RP_N];   // the next round's prepare: the sums of the bucket's ranges
     const uint32_t W = 1u << wshift, wmask = W - 1, b = blockIdx.x;
     uint32_t* cnt = sm;
     uint32_t* bs = sm + W;
@@ -1033,6 +1268,21 @@ __global__ void __launch_bounds__(RR_THREADS) k_bucket_route(
     }
     pairs += q0;                                      // (pair i of the bucket at pairs[i], its rank at rank[i])
     rank += q0;
+    // the next round's prepare (a block that returned above does none of it:
+    // a reroute still finds this round's ocnt): the flag bytes -- final, this
+    // round's node phases ran before its route -- and the start words of the
+    // thread's first nodes, issued here and used after the counting pass
+    constexpr bool prep = PREP && !WIRE;
+    uint8_t pf[RP_NODES] = {};
+    uint32_t pst[RP_NODES] = {};
+    if (prep) {
+#pragma unroll
+        for (uint32_t k = 0; k < RP_NODES; k++) {
+            const uint32_t d = (b << wshift) + threadIdx.x + k * RR_THREADS;
+            if (d < n) { pf[k] = rp.flags[rp.lo + d]; pst[k] = rp.start[d]; }
+        }
+        for (uint32_t j = threadIdx.x; j < RP_RANGES * RP_N; j += blockDim.x) (&s_rp[0][0])[j] = 0;
+    }
     // the bucket's run-ordered source indices: in LDS after the 4 W words when
     // they fit (lcap > 0: the host sized the dynamic LDS for them; round 6 --
     // in memory, the runs' sorts and the gather each read back what the
@@ -1084,11 +1334,20 @@ __global__ void __launch_bounds__(RR_THREADS) k_bucket_route(
         uint32_t tot;
         spart[threadIdx.x] = block_excl<uint32_t, RR_THREADS>(sum, &tot) + sum;   // (inclusive)
     }
-    for (uint32_t dl = threadIdx.x; dl < W; dl += blockDim.x) {
+    // (the next round's prepare keeps the thread's bound sums and masks: it
+    // runs after the run placement, when the pairs' registers are free)
+    uint32_t pbs[RP_NODES] = {};
+    unsigned long long pmk[RP_NODES] = {};
+    for (uint32_t dl = threadIdx.x, k = 0; dl < W; dl += blockDim.x, k++) {
         const uint32_t d = (b << wshift) + dl;
         if (d >= n) break;
-        cb[d] = cnt[dl] | ((unsigned long long)bs[dl] << 32);
-        bmask[d] = mk[dl];
+        const uint32_t bv = bs[dl];
+        const unsigned long long mv = mk[dl];
+        cb[d] = cnt[dl] | ((unsigned long long)bv << 32);
+        bmask[d] = mv;
+        if (prep) {                                   // (W = RP_NODES * RR_THREADS: the host's condition)
+            if (k == 0) { pbs[0] = bv; pmk[0] = mv; } else { pbs[RP_NODES - 1] = bv; pmk[RP_NODES - 1] = mv; }
+        }
     }
     __syncthreads();                                  // the bound sums are out: pre reuses them
     uint32_t run = spart[threadIdx.x] - sum;
@@ -1118,6 +1377,53 @@ __global__ void __launch_bounds__(RR_THREADS) k_bucket_route(
         }
     }
     __syncthreads();                                  // the runs are in place (same block)
+#ifndef PSIM_BOUND_TERMS
+    if (prep) {
+        // each of the thread's nodes as k_node_prep would take it in a round
+        // without events (origin 0: a batch's origins are spent in its first
+        // round); a wave's 64 nodes lie in one range (a multiple of BLK
+        // nodes): its sums go to the range's LDS row.  No store before the
+        // second node's loads (gfx9 counts loads and stores in one in-order
+        // counter)
+        uint64_t pk[RP_NODES];
+#pragma unroll
+        for (uint32_t k = 0; k < RP_NODES; k++) {
+            const uint32_t dl = threadIdx.x + k * RR_THREADS, d = (b << wshift) + dl;
+            PrepSums ps{0, 0, 0, 0, 0, 0};
+            pk[k] = 0;
+            if (d < n)
+                pk[k] = hv_node_prep<false>(rp, d, pf[k], cnt[dl] | ((unsigned long long)pbs[k] << 32), pmk[k], pst[k],
+                                            0u, ps);
+            const uint32_t uwq = wave_sum((uint32_t)ps.up | (uint32_t)ps.ws << 10 | (uint32_t)ps.qp << 20);
+            // (messages to dead nodes, quiet ticks' failed sends and bounds past
+            // 2^24 slots a node: none in most waves)
+            const uint32_t drop = wave_sum_rare((uint32_t)ps.drop), qf = wave_sum_rare((uint32_t)ps.qf);
+            const uint32_t blo = wave_sum((uint32_t)ps.bs & 0xFFFFFFu);   // (64 x 24 bits: no carry lost)
+            const unsigned long long bhi = (unsigned long long)wave_sum_rare((uint32_t)(ps.bs >> 24) & 0xFFFFFFu) +
+                                           ((unsigned long long)wave_sum_rare((uint32_t)(ps.bs >> 48)) << 24);
+            if ((threadIdx.x & 63) == 0) {
+                uint32_t* row = s_rp[dl >> rp.pshift];
+                if (uwq) {                            // (a wave's counts: 7 bits each)
+                    atomicAdd(&row[RP_UP], uwq & 0x3FFu);
+                    atomicAdd(&row[RP_W], (uwq >> 10) & 0x3FFu);
+                    atomicAdd(&row[RP_QP], uwq >> 20);
+                }
+                if (drop) atomicAdd(&row[RP_DROP], drop);
+                if (qf) atomicAdd(&row[RP_QF], qf);
+                const unsigned long long bsum = blo + (bhi << 24);
+                if (bsum) atomicAdd(reinterpret_cast<unsigned long long*>(&row[RP_BLO]), bsum);
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < RP_NODES; k++) {
+            const uint32_t d = (b << wshift) + threadIdx.x + k * RR_THREADS;
+            if (d < n) {
+                rp.packed[d] = pk[k];
+                rp.ocnt[d] = 0;                       // consume writes the count of every node it runs
+            }
+        }
+    }
+#endif
     // the bucket's longer runs, listed in LDS (the BROADCAST masks are out:
     // their words hold the list and the block sort's buffer)
     uint32_t* sv = reinterpret_cast<uint32_t*>(mk);   // RUN_LDS words
@@ -1147,6 +1453,28 @@ __global__ void __launch_bounds__(RR_THREADS) k_bucket_route(
             if (t < k) q[t] = v[t];
     }
     __syncthreads();
+    if (prep) {
+        // the bucket's ranges, a wave each: the range's sum of packed words
+        // and its exact bound for k_desc, its stats row (k_bucket_fill folded
+        // this round's rows into tiles before this launch; block 0 read only
+        // the tiles)
+        const uint32_t nrb = max(1u, W >> rp.pshift), c = threadIdx.x & 63;
+        for (uint32_t j = threadIdx.x >> 6; j < nrb; j += blockDim.x >> 6) {
+            const uint32_t R = ((b << wshift) >> rp.pshift) + j;
+            if (R >= rp.nranges) break;
+            const uint64_t up = s_rp[j][RP_UP], ws = s_rp[j][RP_W], qp = s_rp[j][RP_QP];
+            const unsigned long long bsum = *reinterpret_cast<const unsigned long long*>(&s_rp[j][RP_BLO]);
+            if (c == 0) {
+                rp.tiles[R] = ((uint64_t)bsum << 32) + ws;
+                rp.btot[R] = bsum;
+                if (R == rp.nranges - 1) rp.tiles[rp.nranges] = 0;
+            }
+            if (c < NST)
+                rp.part[(size_t)R * NST + c] = c == ST_UP ? up : c == ST_DROPPED ? (uint64_t)s_rp[j][RP_DROP]
+                                             : c == ST_PROC ? qp : c == ST_FAIL ? (uint64_t)s_rp[j][RP_QF]
+                                             : c == ST_BYTES ? ws * (2 * NODE_STATE_BYTES) : 0ull;
+        }
+    }
     // runs of RUN_SHORT + 1 .. 64: one wave each (a bitonic network over the
     // lanes); longer ones -- a join storm on one contact -- the whole block
     const uint32_t nl = s_nl, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
@@ -1178,24 +1506,6 @@ __global__ void __launch_bounds__(RR_THREADS) k_bucket_route(
     }
 }
 
-constexpr uint64_t NODE_STATE_BYTES = 416;   // SURVEY 8(d): HyParView 304 + Plumtree 112 per node
-
-__device__ __forceinline__ bool due(uint32_t period, uint32_t r, uint32_t start) {
-    return period > 0 && r > start && ((r - start) % period) == 0;
-}
-
-#ifdef PSIM_BOUND_TERMS
-// diagnostic build (make evariant V=bterms X=-DPSIM_BOUND_TERMS): the outbox
-// bound's terms summed over the nodes of every round since psim_step last
-// printed them (PSIM_TRACE_BOUND)
-enum { BT_RESP, BT_TIMER, BT_PUSH, BT_PUSH_NE, BT_NPUSH, BT_LAZY, BT_ON, BT_NL, BT_LC, BT_CRASH, BT_XBOT,
-       BT_BUMP, BT_TOTAL, BT_C, BT_QUIET, BT_ROUNDS, BT_N };
-__device__ unsigned long long g_bterm[BT_N];
-#define BTERM(k, v) (bt[k] += (v))
-#else
-#define BTERM(k, v) ((void)0)
-#endif
-
 // Per local node: the upper bound of its emissions this round (sizes its
 // outbox region) and whether it has any work (inbox, join, timers, EXIT
 // scan, origin, outstanding lazy pushes).  Also counts live nodes and
@@ -1223,8 +1533,7 @@ __global__ void __launch_bounds__(BLK) k_node_prep(RoundArgs a, const unsigned l
     if (a.upart && a.upart_dirty)
         for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < a.n_nodes; g += gridDim.x * blockDim.x)
             a.upart[g] = (a.flags[g] & F_UP) ? (upart_t)a.part[g] : UPART_DOWN;
-    unsigned long long up = 0, drop = 0, bs = 0, ws = 0;   // this thread's sums (wave-summed below)
-    unsigned long long qp = 0, qf = 0;                     // quiet lazy ticks: nodes, failed sends
+    PrepSums ps{0, 0, 0, 0, 0, 0};                     // this thread's sums (wave-summed below)
 #ifdef PSIM_BOUND_TERMS
     unsigned long long bt[BT_N] = {};
 #endif
@@ -1257,179 +1566,37 @@ __global__ void __launch_bounds__(BLK) k_node_prep(RoundArgs a, const unsigned l
     // store waits for it -- the node's row loads behind the last node's
     // stores were a store latency per node, 64 nodes a thread at 2^26)
     auto node = [&](uint32_t i, const PrepIn& cur) -> uint64_t {
-        uint8_t f = cur.f;
+        if (!a.pl) return hv_node_prep<true>(a, i, cur.f, cur.cbi, cur.bm, cur.st, cur.org, ps BT_ARG);
         uint64_t b = 0;
         uint32_t w = 0;
-        const unsigned long long cbi = cur.cbi;
-        uint32_t c = (uint32_t)cbi;
-        const uint32_t st_ = cur.st;
-        const uint32_t org_ = cur.org;
-        const unsigned long long bm_ = cur.bm;
-        if (f & F_UP) {
-            uint32_t st = st_, r = a.round;
-            if (a.pl) {            // emission bounds of the pluggable round (R0-P)
-                const Hdr& x = a.hdr[i];
-                bool pending = x.join_contact != PSIM_NONE;
-                bool per = due(a.periodic, r, st);
-                bool leave = x.pad1[0] != 0;
-                if (a.strategy == PSIM_STRATEGY_FULL)
-                    b = a.fanout ? (uint64_t)c + a.fanout + 1
-                                 : ((uint64_t)c + 2 + (leave ? 1 : 0)) * (a.n_nodes + 1);
-                else
-                {
-                    // the view at round start, grown by at most one id per
-                    // inbox message (a kept subscription) and the contact:
-                    // join = contact + members + picks, periodic = a
-                    // resubscription + a ping per member, leave/1 (before
-                    // the inbox) = one per member, any message = one send
-                    const uint64_t vn = x.act_n, vg = vn + c + 1;
-                    b = (uint64_t)c + (pending ? 1 + 2 * vg : 0) + (per ? 1 + vg : 0) + (leave ? vn : 0) + 1;
-                }
-                w = c > 0 || (pending && !x.have) || per || leave;
-            } else {
-                bool origin = org_ != 0;
-                const Hdr& x = a.hdr[i];      // (read only where needed: a fresh start, a full nibble)
-                // the due timers' sends: the JOIN of a fresh start, a
-                // promotion's NEIGHBOR_REQUEST (the active view may shrink
-                // during the round: any due promotion), a shuffle
-                const bool promo = a.random_promotion && due(a.promotion_period, r, st);
-                b = (cbi >> 32) + (st == r && x.join_contact != PSIM_NONE ? 1u : 0u) + (promo ? 1u : 0u) +
-                    (due(a.shuffle_period, r, st) ? 1u : 0u);
-                BTERM(BT_RESP, cbi >> 32);
-                BTERM(BT_TIMER, b - (cbi >> 32));
-                // per BROADCAST message slot a first delivery's eager push
-                // and lazy adds (plus the origin's): at most the root's sets
-                // at round start -- or the common eagers of a new root or of a
-                // reset -- plus one per message handled before; the push's
-                // sends need an active connection: at most two per active
-                // member (its atom and its node_spec identity, App. A Q6)
-                // (round 6: a slot's pushes and lazy adds together are at most
-                // the root's eager and lazy sets at round start -- or the
-                // common eagers of a new root or a reset -- plus one per
-                // message handled before: update_peers/5 (pt:593-609) adds one
-                // peer a message to their union, and the pushes go to the
-                // eager set, the adds to the lazy one (pt:374-378))
-                const unsigned long long bm = c ? bm_ : 0ull;
-                const uint32_t pushes = (uint32_t)__popcll(bm) + (origin ? 1u : 0u);
-                const bool lazy = a.plumtree && due(a.lazy_tick_period, r, st);
-                uint32_t lazy_add = 0, push_sum = 0, union_sum = 0;
-                if (pushes) {
-                    const uint4 r0 = *reinterpret_cast<const uint4*>(a.pt_rt + (size_t)i * RT_WORDS);
-                    const uint2 cn = *reinterpret_cast<const uint2*>(a.pt_rt + (size_t)i * RT_WORDS + RT_EN);
-                    const uint32_t rts[4] = {r0.x, r0.y, r0.z, r0.w};
-                    auto push = [&](uint32_t root) {
-                        uint32_t ne = PSIM_PT_MEMBERS_CAP, nl = 0, ne0 = 0;
-#pragma unroll
-                        for (int k = 0; k < PSIM_PT_ROOTS; k++)
-                            if (rts[k] == root) {
-                                ne0 = (cn.x >> (8 * k)) & 0xFFu;
-                                ne = max(ne, ne0);
-                                nl = (cn.y >> (8 * k)) & 0xFFu;
-                            }
-                        const uint32_t pb = min(2u * PSIM_ACTIVE_CAP, ne + c);
-                        push_sum += pb;
-                        lazy_add += nl + c;
-                        union_sum += min(pb + nl + c, max((uint32_t)PSIM_PT_MEMBERS_CAP, ne0 + nl) + c);
-                        BTERM(BT_PUSH, min(2u * PSIM_ACTIVE_CAP, ne + c));
-                        BTERM(BT_PUSH_NE, min(2u * PSIM_ACTIVE_CAP, ne));
-                        BTERM(BT_NPUSH, 1);
-                        BTERM(BT_NL, nl);
-                        BTERM(BT_LC, c);
-                    };
-                    for (unsigned long long m = bm; m; m &= m - 1) push(a.slots[PSIM_MSG_SLOTS + __ffsll(m) - 1]);
-                    if (origin) push((a.lo + i) | PSIM_MAP_BIT);
-                }
-                // a due lazy tick sends every outstanding entry: those left
-                // from last round and those this round's pushes add, at most
-                // PT_OUT_CAP
-                // (the flag byte's nibble is min(out_n, 15) after the node's
-                // last round: the header only when it saturates)
-                // (with the tick: the pushes P and the tick's IHAVEs, at most
-                // min(PT_OUT_CAP, on + L), where P + L is at most the slots'
-                // union term)
-                if (lazy) {
-                    const uint32_t fo = (uint32_t)f >> F_OUTN_SHIFT;
-                    const uint32_t on = fo < 15 ? fo : (uint32_t)x.out_n;
-                    const uint32_t pl = min(push_sum + min((uint32_t)PSIM_PT_OUT_CAP, on + lazy_add), on + union_sum);
-                    b += pl;
-                    BTERM(BT_LAZY, pl - push_sum);
-                    BTERM(BT_ON, on);
-                } else {
-                    b += push_sum;
-                }
-                if (pushes) BTERM(BT_C, c);
-                // a crash round: a NEIGHBOR_REQUEST per crashed active member
-                // (bounded over every crashed member); EXIT work for a
-                // crashed member held over a connection -- an active member
-                // not marked PSIM_CONN_DOWN, or a lingering peer (App. A Q11)
-                bool exits = false;
-                if (a.crash_round) {
-                    const uint4* ar = reinterpret_cast<const uint4*>(a.act + (size_t)i * PSIM_ACTIVE_CAP);
-                    const uint4 a0 = ar[0], a1 = ar[1];
-                    const uint32_t av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                    uint32_t cv[PSIM_CONN_CAP] = {};
-                    const uint32_t cn = x.conn_n;
-                    if (cn) {
-                        const uint4* cr = reinterpret_cast<const uint4*>(a.conn + (size_t)i * PSIM_CONN_CAP);
-                        const uint4 c0 = cr[0], c1 = cr[1];
-                        cv[0] = c0.x; cv[1] = c0.y; cv[2] = c0.z; cv[3] = c0.w;
-                        cv[4] = c1.x; cv[5] = c1.y; cv[6] = c1.z; cv[7] = c1.w;
-                    }
-#pragma unroll
-                    for (int k = 0; k < PSIM_ACTIVE_CAP; k++)
-                        if ((uint32_t)k < x.act_n && av[k] < a.n_nodes && av[k] != a.lo + i &&
-                            crashed_now(a, av[k])) {
-                            b++;
-                            BTERM(BT_CRASH, 1);
-                            bool down = false;
-#pragma unroll
-                            for (int j = 0; j < PSIM_CONN_CAP; j++) down |= (uint32_t)j < cn && cv[j] == (av[k] | PSIM_CONN_DOWN);
-                            exits |= !down;
-                        }
-#pragma unroll
-                    for (int j = 0; j < PSIM_CONN_CAP; j++)
-                        exits |= (uint32_t)j < cn && !(cv[j] & PSIM_CONN_DOWN) && crashed_now(a, cv[j] & KEY_DST_MASK);
-                }
-                // a quiet node (entries outstanding, F_LAZY clear: its last
-                // tick reached no peer) runs only for other work: its tick
-                // fails every entry again (pt:443-453 over send/3), counted
-                // here -- the node processed, a failed send per entry.  Only
-                // with a tick every round (else a round without one could
-                // connect a peer unseen) and no waking event
-                const uint32_t fon = (uint32_t)f >> F_OUTN_SHIFT;
-                const bool quiet_ok = a.lazy_tick_period == 1 && !a.lazy_wake && !(f & F_LAZY);
-                w = c > 0 || st == r || exits || (fon && !quiet_ok) || origin ||
-                    (a.random_promotion && (f & F_LOWACT) && due(a.promotion_period, r, st)) ||
-                    due(a.shuffle_period, r, st);
-                if (a.xbot) {
-                    // X-BOT: a due xbot_execution sends to two candidates at
-                    // most; the 'EXIT' of each connection pid stopped last
-                    // round may promote (a NEIGHBOR_REQUEST each)
-                    const bool xb = due(a.xbot_period, r, st);
-                    const uint32_t cl = x.conn_cl;
-                    b += (xb ? 2u : 0u) + cl;
-                    BTERM(BT_XBOT, (xb ? 2u : 0u) + cl);
-                    w = w || xb || cl;
-                }
-                // a working node's first slot is reserved: a wave that emits
-                // nothing rewrites it (flush_recs' fixed store)
-                if (w && b == 0) { b = 1; BTERM(BT_BUMP, 1); }
-                if (!w && fon && lazy) {
-                    qp++;
-                    qf += fon < 15 ? fon : (uint32_t)x.out_n;
-                    BTERM(BT_QUIET, 1);
-                    b = 0;
-                }
+        const uint32_t c = (uint32_t)cur.cbi;
+        if (cur.f & F_UP) {        // emission bounds of the pluggable round (R0-P)
+            const uint32_t st = cur.st, r = a.round;
+            const Hdr& x = a.hdr[i];
+            bool pending = x.join_contact != PSIM_NONE;
+            bool per = due(a.periodic, r, st);
+            bool leave = x.pad1[0] != 0;
+            if (a.strategy == PSIM_STRATEGY_FULL)
+                b = a.fanout ? (uint64_t)c + a.fanout + 1
+                             : ((uint64_t)c + 2 + (leave ? 1 : 0)) * (a.n_nodes + 1);
+            else
+            {
+                // the view at round start, grown by at most one id per
+                // inbox message (a kept subscription) and the contact:
+                // join = contact + members + picks, periodic = a
+                // resubscription + a ping per member, leave/1 (before
+                // the inbox) = one per member, any message = one send
+                const uint64_t vn = x.act_n, vg = vn + c + 1;
+                b = (uint64_t)c + (pending ? 1 + 2 * vg : 0) + (per ? 1 + vg : 0) + (leave ? vn : 0) + 1;
             }
-            up++;
+            w = c > 0 || (pending && !x.have) || per || leave;
+            ps.up++;
         } else {
-            drop += c;
+            ps.drop += c;
         }
-        bs += b;
-        ws += w;
+        ps.bs += b;
+        ps.ws += w;
         BTERM(BT_TOTAL, b);
-        // one scan gives both the outbox base (high word: the bounds) and
-        // the position in the active list (low word: the work flags)
         return (b << 32) | w;
     };
     // PREP_CHUNK nodes a thread at a time: their inputs loaded together (the
@@ -1468,20 +1635,20 @@ __global__ void __launch_bounds__(BLK) k_node_prep(RoundArgs a, const unsigned l
     }
 #endif
     for (int o = 32; o > 0; o >>= 1) {
-        up += __shfl_xor(up, o);
-        drop += __shfl_xor(drop, o);
-        bs += __shfl_xor(bs, o);
-        ws += __shfl_xor(ws, o);
-        qp += __shfl_xor(qp, o);
-        qf += __shfl_xor(qf, o);
+        ps.up += __shfl_xor(ps.up, o);
+        ps.drop += __shfl_xor(ps.drop, o);
+        ps.bs += __shfl_xor(ps.bs, o);
+        ps.ws += __shfl_xor(ps.ws, o);
+        ps.qp += __shfl_xor(ps.qp, o);
+        ps.qf += __shfl_xor(ps.qf, o);
     }
     if ((threadIdx.x & 63) == 0) {
-        if (up) atomicAdd(&s_up, up);
-        if (drop) atomicAdd(&s_drop, drop);
-        if (bs) atomicAdd(&s_b, bs);
-        if (ws) atomicAdd(&s_w, ws);
-        if (qp) atomicAdd(&s_qp, qp);
-        if (qf) atomicAdd(&s_qf, qf);
+        if (ps.up) atomicAdd(&s_up, ps.up);
+        if (ps.drop) atomicAdd(&s_drop, ps.drop);
+        if (ps.bs) atomicAdd(&s_b, ps.bs);
+        if (ps.ws) atomicAdd(&s_w, ps.ws);
+        if (ps.qp) atomicAdd(&s_qp, ps.qp);
+        if (ps.qf) atomicAdd(&s_qf, ps.qf);
     }
     __syncthreads();
     // the tile's sum of the packed words (wrapping like them past 2^32
@@ -1588,8 +1755,25 @@ __global__ void __launch_bounds__(PREP_BLK) k_desc(const uint64_t* __restrict__ 
                                                   const uint32_t* __restrict__ start, RoundArgs a,
                                                   uint4* __restrict__ desc, uint64_t* __restrict__ obase,
                                                   uint32_t* nact, const unsigned long long* btot,
-                                                  uint32_t nranges, uint64_t* hout, uint64_t cap, uint32_t* ctl) {
+                                                  uint32_t nranges, uint64_t* hout, uint64_t cap, uint32_t* ctl,
+                                                  uint32_t* gcnt, uint32_t ngcnt) {
     if (*ctl) return;                                 // (uniform)
+    // a round the route prepared (RoutePrep) launched no k_node_prep: its
+    // once-a-round resets here (gcnt != nullptr) -- the fused route's bucket
+    // counters and overflow flag (the last route has read them, every block all
+    // of them; the next k_bucket_fill counts into them), the phase kernels'
+    // list counts and the span stamps
+    if (gcnt) {
+        for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < ngcnt; j += gridDim.x * blockDim.x) gcnt[j] = 0;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            ctl[2] = 0;
+            a.ktime[0] = ~0ull; a.ktime[1] = 0; *a.n_slow = 0; *a.n_pt = 0;
+            if (a.n_shuf) *a.n_shuf = 0;
+            if (a.n_lite) { a.n_lite[0] = 0; a.n_lite[1] = 0; a.n_lite[2] = 0; a.n_lite[3] = 0; }
+            if (a.n_ptl) { a.n_ptl[0] = 0; a.n_ptl[1] = 0; a.n_ptl[2] = 0; a.n_ptl[3] = 0; }
+            if (a.n_stop) *a.n_stop = 0;
+        }
+    }
     const bool last = blockIdx.x == gridDim.x - 1;
     const uint32_t r0 = blockIdx.x * DESC_RANGES;     // this block's first k_node_prep range
     const uint32_t i0 = r0 * per, i1 = min(a.n_local, i0 + DESC_RANGES * per);
@@ -2209,6 +2393,11 @@ struct Shard {
     uint64_t desc_cap = 0;
     uint32_t batch_round1 = 0;
     uint32_t stat_slot = 0;
+    // a batch's route prepares the next round (RoutePrep, PSIM_PREP_FUSED):
+    // prep_next = that round + 1 while its route is enqueued (0: no), and
+    // prepared = the round being enqueued was prepared by the last route
+    uint32_t prep_next = 0;
+    bool prepared = false;
     bool outx_short = false;            // the outstanding pool failed to grow (reported once per shard)
     // the rank path's batches (run_batch_ranked): the fixed per-owner
     // capacities of the exchange (heads, tails; 0 = not known yet: no batch),
@@ -2317,6 +2506,44 @@ int ptl_early_knob() {
         return x >= 0 && x <= 2 ? x : PTL_EARLY_DEFAULT;
     }();
     return v;
+}
+
+// PSIM_PREP_FUSED, read once: 1 = inside a batch the route of a round without
+// a round-end half prepares the next round (k_bucket_route, RoutePrep) and
+// that round launches no k_node_prep; 0 = every round launches k_node_prep.
+constexpr int PREP_FUSED_DEFAULT = 1;
+bool prep_fused_knob() {
+#ifdef PSIM_BOUND_TERMS
+    return false;                       // (the diagnostic sums live in k_node_prep)
+#else
+    static const bool v = [] {
+        const char* e = getenv("PSIM_PREP_FUSED");
+        return e && *e ? atoi(e) != 0 : PREP_FUSED_DEFAULT != 0;
+    }();
+    return v;
+#endif
+}
+
+// the route's bucket width: 2^wshift destinations
+// Up to 2^22 nodes 2048-node buckets: twice the route's blocks (one per
+// CU at 2^20 with 4096) -- k_bucket_route 64 -> 56 us, the histogram
+// passes +4 us, the step 0.667 -> 0.663 ms (profiles/r05/ab_log.txt r5o);
+// in round 3, before the gather moved into the route, 1024-node buckets
+// measured 1 % slower a step (profiles/r03/ab_log.txt, p17)
+uint32_t route_wshift(uint32_t n) {
+    uint32_t wshift = n > (1u << 26) ? 13 : n > (1u << 22) ? 12 : 11;
+    static const int env = getenv("PSIM_ROUTE_WSHIFT") ? atoi(getenv("PSIM_ROUTE_WSHIFT")) : 0;   // (another width, for measurements)
+    if (env >= (int)WSHIFT_MIN && env <= (int)WSHIFT_MAX) wshift = (uint32_t)env;
+    return wshift;
+}
+
+// Whether this handle's batches may prepare rounds in the route: the fused
+// local route of a HyParView / X-BOT handle.  Its prepare ranges are then a
+// power of two of nodes (prepare_ranges), and nest in the buckets where they
+// are no wider than one
+bool prep_fused_handle(const psim_handle* h, const Shard* s) {
+    return prep_fused_knob() && h->G == 1 && !h->ranked && h->route_fused && s->n <= (1u << 26) &&
+           h->cfg.manager != PSIM_MANAGER_PLUGGABLE;
 }
 
 RoundArgs make_args(psim_handle* h, Shard* s) {
@@ -2512,10 +2739,12 @@ int scan_excl(Shard* s, const TI* in, T* out, uint32_t n) {
 // prepare's scan + descriptors: k_node_prep left its blocks' range sums in
 // pscan[0..pgrid); k_desc sums the ones before its range and walks the range
 // again
-int scan_desc(Shard* s, const RoundArgs& a) {
+// resets: the route prepared this round, so k_desc does k_node_prep's resets
+int scan_desc(Shard* s, const RoundArgs& a, bool resets = false) {
     k_desc<<<(s->pgrid + DESC_RANGES - 1) / DESC_RANGES, PREP_BLK, 0, s->stream>>>(
         s->bound.p, s->pscan.p, s->pper, s->in_beg.p, s->cb.p, s->start.p, a, s->desc.p, s->obase.p, s->d_nact.p,
-        s->btot.p, s->pgrid, s->pin_dev, s->desc_cap, s->ctl.p);
+        s->btot.p, s->pgrid, s->pin_dev, s->desc_cap, s->ctl.p, resets ? s->gcnt.p : nullptr,
+        resets ? (uint32_t)s->gcnt.n : 0u);
     HIP_TRY(hipGetLastError());
     return PSIM_OK;
 }
@@ -2563,8 +2792,10 @@ struct RoundCtl {
 // run_batch_ranked: they are still pending on the host, and the round is an
 // event round all the same); batched: no host wait -- the outbox and route
 // capacities stand and k_desc checks the outbox on the device (desc_cap)
+// prepared: the last route prepared this round (RoutePrep; no events, batched):
+// no k_node_prep launch, and k_desc does its resets
 int phase_events_prepare(psim_handle* h, Shard* s, const RoundCtl& ctl, RoundArgs& a, bool events = true,
-                         bool batched = false, bool redo = false) {
+                         bool batched = false, bool redo = false, bool prepared = false) {
     const uint32_t n = s->n;
     if (events && h->faults_dirty) {    // interposition funs installed / removed
         std::vector<uint64_t> keys(h->nx_omit_s.begin(), h->nx_omit_s.end());
@@ -2637,6 +2868,11 @@ int phase_events_prepare(psim_handle* h, Shard* s, const RoundCtl& ctl, RoundArg
         {
             const uint32_t g = std::min<uint32_t>(std::max<uint32_t>(1, grid_for(n) / PREP_NPT), DESC_RANGES * PREP_BLK);
             s->pper = BLK * (uint32_t)(((uint64_t)n + (uint64_t)g * BLK - 1) / ((uint64_t)g * BLK));
+            // (where the route may prepare rounds the next power of two: the
+            // ranges then divide the route's buckets or are multiples of one --
+            // the scan is exact, so the partition changes no result)
+            if (prep_fused_handle(h, s))
+                while (s->pper & (s->pper - 1)) s->pper += s->pper & (0u - s->pper);
             s->pgrid = std::max<uint32_t>(1, (uint32_t)(((uint64_t)n + s->pper - 1) / s->pper));
         }
         s->cgrid = std::min<uint32_t>(grid_for(n), h->consume_blocks);
@@ -2658,11 +2894,12 @@ int phase_events_prepare(psim_handle* h, Shard* s, const RoundCtl& ctl, RoundArg
         s->egrid = ptl_early_knob() ? s->qgrid : 0;
         TRY(s->stat_part.ensure((size_t)(s->pgrid + s->cgrid + s->rgrid + s->tgrid + s->sgrid + s->lgrid + s->qgrid + s->egrid) *
                                 NST));
-        k_node_prep<<<s->pgrid, BLK, 0, s->stream>>>(a, s->bmask.p, s->bound.p, s->stat_part.p, s->ocnt.p,
-                                                     s->btot.p, s->pper, s->pscan.p, s->gcnt.p, (uint32_t)s->gcnt.n);
+        if (!prepared)
+            k_node_prep<<<s->pgrid, BLK, 0, s->stream>>>(a, s->bmask.p, s->bound.p, s->stat_part.p, s->ocnt.p,
+                                                         s->btot.p, s->pper, s->pscan.p, s->gcnt.p, (uint32_t)s->gcnt.n);
         // (pscan: the ranges' sums of packed words; k_desc's last block sums them all)
         // obase[n] = the exact total (btot, summed by k_desc's last block)
-        TRY(scan_desc(s, a));
+        TRY(scan_desc(s, a, prepared));
         if (batched) goto args;
         TRY(stream_wait(s));                          // (k_desc stored the total in pin)
         if (s->pin[PIN_BIGIN]) { s->pin[PIN_BIGIN] = 0; return PSIM_ENOMEM; }   // an inbox count must fit 27 bits
@@ -2866,17 +3103,8 @@ unsigned long long* phase_end_mark(psim_handle* h, Shard* s) {
 int route_group(psim_handle* h, Shard* s, bool dense, uint32_t m, bool fixed = false, bool exact = false) {
     const uint32_t n = s->n;
     // buckets of 2^wshift destinations, one k_bucket_route block each, at
-    // most 16 K of them (the two passes' LDS histograms: 4 B per bucket).
-    // Up to 2^22 nodes 2048-node buckets: twice the route's blocks (one per
-    // CU at 2^20 with 4096) -- k_bucket_route 64 -> 56 us, the histogram
-    // passes +4 us, the step 0.667 -> 0.663 ms (profiles/r05/ab_log.txt r5o);
-    // in round 3, before the gather moved into the route, 1024-node buckets
-    // measured 1 % slower a step (profiles/r03/ab_log.txt, p17)
-    uint32_t wshift = n > (1u << 26) ? 13 : n > (1u << 22) ? 12 : 11;
-    if (const char* e = getenv("PSIM_ROUTE_WSHIFT")) {  // (another bucket width, for measurements)
-        const int v = atoi(e);
-        if (v >= (int)WSHIFT_MIN && v <= (int)WSHIFT_MAX) wshift = (uint32_t)v;
-    }
+    // most 16 K of them (the two passes' LDS histograms: 4 B per bucket)
+    const uint32_t wshift = route_wshift(n);
     const uint32_t W = 1u << wshift, nb = (n + W - 1) >> wshift;
     const RouteIn in{s->outbox.p, s->okey.p, s->obase.p, s->ocnt.p, dense ? m : n, s->lo,
                      h->cfg.manager == PSIM_MANAGER_PLUGGABLE, dense ? s->recvh.p : nullptr,
@@ -2921,12 +3149,34 @@ int route_group(psim_handle* h, Shard* s, bool dense, uint32_t m, bool fixed = f
         TRY(s->pairs.ensure((size_t)nb * capb));
         TRY(s->rank.ensure((size_t)nb * capb));
         static const uint32_t walk = getenv("PSIM_FILL_WALK") && atoi(getenv("PSIM_FILL_WALK")) ? 1u : 0u;
+        // the next round's prepare (run_batch set prep_next: the ranges nest)
+        RoutePrep rp{};
+        if (s->prep_next) {
+            const psim_config& c = h->cfg;
+            uint32_t pshift = 0;
+            while ((1u << pshift) < s->pper) pshift++;
+            rp.round = s->prep_next - 1; rp.n_nodes = h->N; rp.lo = s->lo;
+            rp.shuffle_period = c.shuffle_period; rp.promotion_period = c.promotion_period;
+            rp.random_promotion = c.random_promotion; rp.plumtree = c.plumtree;
+            rp.lazy_tick_period = c.lazy_tick_period;
+            rp.xbot = c.manager == PSIM_MANAGER_XBOT; rp.xbot_period = c.xbot_period;
+            rp.pshift = pshift; rp.nranges = s->pgrid;
+            rp.flags = s->flags.p; rp.hdr = s->hdr.p; rp.pt_rt = s->pt_rt.p; rp.slots = s->slots.p;
+            rp.start = s->start.p; rp.packed = s->bound.p; rp.ocnt = s->ocnt.p; rp.tiles = s->pscan.p;
+            rp.btot = s->btot.p; rp.part = s->stat_part.p;
+        }
         k_bucket_fill<false><<<nblk, RB_STEP, lds_h, s->stream>>>(in, nsteps, nb, wshift, s->gcnt.p, capb, s->pairs.p,
                                                                   s->ctl.p, phase_end_mark(h, s), st, walk);
-        k_bucket_route<false><<<nb, RR_THREADS, lds_r, s->stream>>>(
-            n, wshift, h->rr_reg, nullptr, s->pairs.p, in.rec, nullptr, nullptr, s->rank.p, s->cb.p, s->bmask.p,
-            s->in_beg.p, s->ivals.p, s->tmp.p, s->inbox.p, s->pin_dev + PIN_M, s->rcap, s->ctl.p, s->gcnt.p, capb,
-            s->batch_round1, st, lcap);
+        if (s->prep_next)
+            k_bucket_route<false, true><<<nb, RR_THREADS, lds_r, s->stream>>>(
+                n, wshift, h->rr_reg, nullptr, s->pairs.p, in.rec, nullptr, nullptr, s->rank.p, s->cb.p, s->bmask.p,
+                s->in_beg.p, s->ivals.p, s->tmp.p, s->inbox.p, s->pin_dev + PIN_M, s->rcap, s->ctl.p, s->gcnt.p, capb,
+                s->batch_round1, st, lcap, rp);
+        else
+            k_bucket_route<false><<<nb, RR_THREADS, lds_r, s->stream>>>(
+                n, wshift, h->rr_reg, nullptr, s->pairs.p, in.rec, nullptr, nullptr, s->rank.p, s->cb.p, s->bmask.p,
+                s->in_beg.p, s->ivals.p, s->tmp.p, s->inbox.p, s->pin_dev + PIN_M, s->rcap, s->ctl.p, s->gcnt.p, capb,
+                s->batch_round1, st, lcap, rp);
         HIP_TRY(hipGetLastError());
         return PSIM_OK;
     }
@@ -2951,12 +3201,12 @@ int route_group(psim_handle* h, Shard* s, bool dense, uint32_t m, bool fixed = f
         k_bucket_route<true><<<nb, RR_THREADS, lds_r, s->stream>>>(
             n, wshift, h->rr_reg, s->rbase.p, s->pairs.p, nullptr, in.wire, in.tails, s->rank.p, s->cb.p, s->bmask.p,
             s->in_beg.p, s->ivals.p, s->tmp.p, s->inbox.p, s->pin_dev + PIN_M, s->rcap, s->ctl.p, nullptr, 0u,
-            s->batch_round1, st, lcap);
+            s->batch_round1, st, lcap, RoutePrep{});
     else
         k_bucket_route<false><<<nb, RR_THREADS, lds_r, s->stream>>>(
             n, wshift, h->rr_reg, s->rbase.p, s->pairs.p, in.rec, nullptr, nullptr, s->rank.p, s->cb.p, s->bmask.p,
             s->in_beg.p, s->ivals.p, s->tmp.p, s->inbox.p, s->pin_dev + PIN_M, s->rcap, s->ctl.p, nullptr, 0u,
-            s->batch_round1, st, lcap);
+            s->batch_round1, st, lcap, RoutePrep{});
     HIP_TRY(hipGetLastError());
     return PSIM_OK;
 }
@@ -3476,14 +3726,26 @@ int run_batch(psim_handle* h, uint32_t nb, psim_round_stats* st_out, uint32_t* d
     s->tn = 0;
     s->desc_cap = batch_desc_cap(h, s);
     const auto t_enq = std::chrono::steady_clock::now();
+    uint32_t n_prepared = 0;
+    s->prepared = false;
     for (uint32_t j = 0; j < nb; j++) {
         s->stat_slot = j + 1;
         s->batch_round1 = (uint32_t)h->round + 1;
         RoundArgs a;
         const RoundCtl ctl = j == 0 ? ctl0 : RoundCtl{};
-        TRY(phase_events_prepare(h, s, ctl, a, j == 0, true));
+        TRY(phase_events_prepare(h, s, ctl, a, j == 0, true, false, s->prepared));
+        n_prepared += s->prepared;
         TRY(phase_consume(h, s, a));
+        // this round's route prepares the next: a later round of the batch
+        // (no events, its origins spent), after a round without a round-end
+        // half (no k_uncrash between the route and it), its ranges no wider
+        // than a bucket (a wider one has several blocks' nodes: k_node_prep)
+        const bool prep = j + 1 < nb && !ctl.crashes && prep_fused_handle(h, s) &&
+                          route_wshift(s->n) == WSHIFT_MIN && s->pper <= (1u << WSHIFT_MIN);
+        s->prep_next = prep ? (uint32_t)h->round + 2 : 0u;
+        s->prepared = prep;
         TRY(phase_route_local(h, s));
+        s->prep_next = 0;
         TRY(phase_stats(h, s, j == 0 ? crashed0 : none));
         if (j == 0 && bc0)                  // the first round's origins are spent
             k_origin<<<grid_for(h->pend_b_root.size()), BLK, 0, s->stream>>>(
@@ -3492,16 +3754,17 @@ int run_batch(psim_handle* h, uint32_t nb, psim_round_stats* st_out, uint32_t* d
         HIP_TRY(hipGetLastError());
         h->round++;
     }
-    s->stat_slot = 0; s->batch_round1 = 0; s->desc_cap = 0;
+    s->stat_slot = 0; s->batch_round1 = 0; s->desc_cap = 0; s->prepared = false;
     uint32_t cw[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(cw, s->ctl.p, sizeof cw, hipMemcpyDeviceToHost, s->stream));
     const auto t_wait = std::chrono::steady_clock::now();
     TRY(stream_wait(s));
     static const bool trace_batch = getenv("PSIM_TRACE_BATCH") != nullptr;
-    if (trace_batch)
-        std::fprintf(stderr, "psim: batch of %u from round %llu: enqueue %.3f ms, wait %.3f ms\n", nb,
-                     (unsigned long long)r0, std::chrono::duration<double, std::milli>(t_wait - t_enq).count(),
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wait).count());
+    if (trace_batch)       // (prepared: the rounds enqueued without a k_node_prep launch, RoutePrep)
+        std::fprintf(stderr, "psim: batch of %u from round %llu: enqueue %.3f ms, wait %.3f ms, %u prepared in the route\n",
+                     nb, (unsigned long long)r0, std::chrono::duration<double, std::milli>(t_wait - t_enq).count(),
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wait).count(),
+                     n_prepared);
     if (s->pin[PIN_BIGIN]) {                          // a node's inbox count must fit 27 bits
         s->pin[PIN_BIGIN] = 0;
         HIP_TRY(hipMemsetAsync(s->ctl.p, 0, sizeof cw, s->stream));

@@ -1,6 +1,8 @@
 """Per-round kernel time by kernel over the last STEPS rounds of a kernel
-trace (a round starts at its k_node_prep; the event kernels launched before
-it count to the round before): mean us per round per kernel name, sorted.
+trace (a round starts at its k_node_prep -- or at its k_desc where the route
+of the round before prepared it and it launched none, PSIM_PREP_FUSED; the
+event kernels launched before it count to the round before): mean us per
+round per kernel name, sorted.
 Usage: python profiles/round_kernels.py run_kernel_trace.csv [STEPS] [--tail TAIL]
 (TAIL: rounds after the window to skip, e.g. bench.py's overlay drain,
 overlay.rounds_drained)"""
@@ -15,7 +17,7 @@ rounds, cur = [], None
 for r in rows:
     name = re.sub(r"\(.*", "", r["Kernel_Name"].replace("(anonymous namespace)::", "")).replace("void ", "").strip()
     d = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-    if "k_node_prep" in name:
+    if "k_node_prep" in name or ("k_desc" in name and (cur is None or any("k_desc" in k for k in cur))):
         cur = {"_start": int(r["Start_Timestamp"])}
         rounds.append(cur)
     if cur is not None:
