@@ -60,7 +60,9 @@ static int get_u32(ErlNifEnv *env, ERL_NIF_TERM map, const char *k, uint32_t *ou
  *         manager => 0 | 1 | 2, strategy => 0 | 1 | 2, fanout => K, scamp_c => C,
  *         periodic_interval => Rounds, xbot_period => Rounds}) -> {ok, Ref}
  * manager 1 = the pluggable manager with strategy 0 full, 1 scamp v1, 2 scamp v2;
- * manager 2 = partisan_hyparview_xbot_peer_service_manager (X-BOT) */
+ * manager 2 = partisan_hyparview_xbot_peer_service_manager (X-BOT);
+ * host_lo => Lo, host_hi => Hi: a host-exchange handle that simulates the ids
+ * [Lo, Hi) and leaves every other id to the host (psim_host_comm_id) */
 static ERL_NIF_TERM nif_create(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
     psim_config c;
     ErlNifUInt64 seed;
@@ -83,6 +85,16 @@ static ERL_NIF_TERM nif_create(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv
     if (enif_get_map_value(env, argv[0], enif_make_atom(env, "seed"), &v) &&
         enif_get_uint64(env, v, &seed))
         c.seed = seed;
+    uint32_t host_lo = 0, host_hi = 0;
+    uint32_t host_id[64];                 /* (psim_create reads the id, it does not keep the pointer) */
+    if (!get_u32(env, argv[0], "host_lo", &host_lo) || !get_u32(env, argv[0], "host_hi", &host_hi))
+        return enif_make_badarg(env);
+    if (host_hi) {
+        if ((size_t)psim_comm_id_size() > sizeof host_id) return err(env, PSIM_EINVAL);
+        int irc = psim_host_comm_id(host_id, sizeof host_id, host_lo, host_hi);
+        if (irc) return err(env, irc);
+        c.comm_id = host_id;
+    }
     sim_res *r = enif_alloc_resource(SIM_RT, sizeof *r);
     r->mu = enif_mutex_create("psim");
     r->n_nodes = c.n_nodes;
@@ -243,6 +255,66 @@ static ERL_NIF_TERM nif_step(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]
     }
     enif_free(st);
     return enif_make_tuple2(env, enif_make_atom(env, "ok"), list);
+}
+
+/* The round of a host-exchange handle (dirty NIFs, under the handle's mutex):
+ * round_emit(Ref) -> ok
+ * outbound(Ref) -> {ok, Binary}: the open round's records for outside nodes,
+ *     64 B each (16 native-endian u32: psim_wire_encode's layout)
+ * round_absorb(Ref, Binary) -> {ok, {Round, Emitted, Delivered, FirstDeliveries}}:
+ *     the records outside nodes sent to owned nodes, in any order; the
+ *     handle's share of the round's stats, as step/2 reports a round */
+static ERL_NIF_TERM nif_round_emit(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+    sim_res *r;
+    if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r)) return enif_make_badarg(env);
+    enif_mutex_lock(r->mu);
+    int rc = psim_round_emit(r->h);
+    enif_mutex_unlock(r->mu);
+    return rc ? err(env, rc) : enif_make_atom(env, "ok");
+}
+
+static ERL_NIF_TERM nif_outbound(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+    sim_res *r;
+    size_t n = 0;
+    ErlNifBinary bin;
+    if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r)) return enif_make_badarg(env);
+    int have_bin = 0;
+    enif_mutex_lock(r->mu);
+    int rc = psim_get_outbound(r->h, NULL, 0, &n);
+    if (!rc) {
+        if (enif_alloc_binary(n * 64, &bin)) have_bin = 1;
+        else rc = PSIM_ENOMEM;
+    }
+    /* (a fresh binary's data is aligned for any type) */
+    if (!rc && n) rc = psim_get_outbound(r->h, (uint32_t *)bin.data, n, &n);
+    enif_mutex_unlock(r->mu);
+    if (rc) {
+        if (have_bin) enif_release_binary(&bin);
+        return err(env, rc);
+    }
+    return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &bin));
+}
+
+static ERL_NIF_TERM nif_round_absorb(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+    sim_res *r; ErlNifBinary b;
+    psim_round_stats st;
+    if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r) || !enif_inspect_binary(env, argv[1], &b) ||
+        b.size % 64)
+        return enif_make_badarg(env);
+    /* (binary data need not be 4-byte aligned: copied into an aligned buffer) */
+    uint32_t *recs = enif_alloc(b.size ? b.size : 4);
+    if (!recs) return err(env, PSIM_ENOMEM);
+    memcpy(recs, b.data, b.size);
+    enif_mutex_lock(r->mu);
+    int rc = psim_round_absorb(r->h, recs, b.size / 64, &st);
+    enif_mutex_unlock(r->mu);
+    enif_free(recs);
+    if (rc) return err(env, rc);
+    uint64_t em = 0, de = 0;
+    for (int t = 0; t < PSIM_MSG_NTYPES; t++) { em += st.emitted[t]; de += st.delivered[t]; }
+    return enif_make_tuple2(env, enif_make_atom(env, "ok"),
+                            enif_make_tuple4(env, enif_make_uint64(env, st.round), enif_make_uint64(env, em),
+                                             enif_make_uint64(env, de), enif_make_uint64(env, st.first_deliveries)));
 }
 
 /* active(Ref, Node) -> {ok, [Id]} : sets:to_list(Active) of one node */
@@ -502,6 +574,9 @@ static ErlNifFunc funcs[] = {
     {"leave_node_nif", 3, nif_leave_node, 0},
     {"broadcast_nif", 3, nif_broadcast, 0},
     {"step", 2, nif_step, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"round_emit", 1, nif_round_emit, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"outbound", 1, nif_outbound, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"round_absorb", 2, nif_round_absorb, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"active_nif", 2, nif_active, 0},
     {"members_nif", 3, nif_members, 0},
     {"delivery_nif", 2, nif_delivery, 0},

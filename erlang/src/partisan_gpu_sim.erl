@@ -11,7 +11,7 @@
          delivery/2, histograms/1, strategy_histograms/1, snapshot/1, restore/2, set_partition/2, clear_partition/1, node/2,
          begin_send_omission/3, end_send_omission/3, begin_receive_omission/3, end_receive_omission/3,
          begin_omission/2, end_omission/2, clear_faults/1, msg_slots/1, set_bucket_table/2, phash_buckets/2,
-         set_phash_table/2, phash_table/2, spec_ip/1]).
+         set_phash_table/2, phash_table/2, spec_ip/1, round_emit/1, outbound/1, round_absorb/2]).
 -on_load(init/0).
 
 %% back-off of a busy handle: 1 ms sleeps, at most ~10 s in all
@@ -39,6 +39,17 @@ leave_node(Sim, Actors, Targets) -> call(fun() -> leave_node_nif(Sim, pack(Actor
 broadcast(Sim, Root, Id) -> call(fun() -> broadcast_nif(Sim, Root, Id) end).
 %% a dirty NIF: waits for the handle's mutex itself
 step(_Sim, _Rounds) -> erlang:nif_error(nif_not_loaded).
+%% A host-exchange handle (create/1 with host_lo and host_hi: the engine
+%% simulates the ids [Lo, Hi), this VM speaks for every other id; every event
+%% call names outside nodes too; step/2 answers {error, unsupported}).  A
+%% round is round_emit/1, outbound/1 -- {ok, Bin}: the records for outside
+%% nodes, 64 B each, 16 native-endian u32 in the wire codec's layout -- and
+%% round_absorb/2 with the records outside nodes sent to owned nodes, in any
+%% order: {ok, {Round, Emitted, Delivered, FirstDeliveries}}, the handle's
+%% share of the round.  Dirty NIFs.
+round_emit(_Sim) -> erlang:nif_error(nif_not_loaded).
+outbound(_Sim) -> erlang:nif_error(nif_not_loaded).
+round_absorb(_Sim, _Records) -> erlang:nif_error(nif_not_loaded).
 active(Sim, Node) -> call(fun() -> active_nif(Sim, Node) end).
 %% pluggable manager handles: the strategy membership of Node (N = n_nodes)
 members(Sim, Node, N) -> call(fun() -> members_nif(Sim, Node, N) end).

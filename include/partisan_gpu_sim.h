@@ -212,7 +212,9 @@ typedef struct psim_config {
                                     a non-NULL id selects the rank path on a one-rank communicator
                                     (the 1-GPU diagnostic of the RCCL path: owner partition,
                                     ncclAllToAll, self ncclSend/ncclRecv, ncclAllReduce,
-                                    ncclAllGather); NULL = the in-place route */
+                                    ncclAllGather); an id from psim_host_comm_id: a
+                                    host-exchange handle over part of the id space (below);
+                                    NULL = the in-place route */
     uint64_t max_msgs_per_round; /* 0 = auto */
     /* pluggable manager */
     uint32_t manager;            /* PSIM_MANAGER_*, 0 = HyParView */
@@ -549,6 +551,17 @@ int psim_wire_encode(const uint32_t rec[16], const psim_wire_names *names, uint8
 int psim_wire_decode(const uint8_t *buf, size_t len, const psim_wire_names *names, uint32_t dst, uint32_t rec[16],
                      size_t *used);
 
+/* Whether a record may enter a handle of this config (host code, beside the
+ * codec: callable without a GPU).  PSIM_EINVAL: a type no handler of
+ * cfg->manager receives (or, under the full strategy, one whose payload lives
+ * in a shard-local arena), or nex > PSIM_EXCHANGE_CAP; PSIM_ERANGE: dst, src,
+ * one of ex[0..nex) or a word the type's handler reads as a node id is >=
+ * cfg->n_nodes -- a Plumtree identity may carry PSIM_MAP_BIT, an IHAVE's root
+ * and X-BOT's DisconnectNode may be PSIM_NONE.  What keeps a wrong frame from
+ * indexing outside a device table: psim_round_absorb copies no unchecked
+ * record to the device. */
+int psim_record_check(const uint32_t rec[16], const psim_config *cfg);
+
 /* Diagnostic: per node-round kernel of the last round (k_relay, k_shuf,
  * the lite kernel, k_consume, k_ptl, k_pt; this process's first shard; the
  * lite kernel is k_lite_quarter, k_lite_half or k_consume_lite), 4 words
@@ -565,7 +578,9 @@ int psim_wire_decode(const uint8_t *buf, size_t len, const psim_wire_names *name
 int psim_debug_kernel_counts(psim_handle *h, uint64_t *out, int cap);
 
 /* Per-kernel device time (ms) accumulated over the last psim_step call:
- * names[i] is a static string; returns the number of entries. */
+ * names[i] is a static string; returns the number of entries.  A
+ * host-exchange handle: over the last round (emit and absorb), the entries
+ * k_host_export and k_host_import included (PSIM_PHASE_TIMERS=1). */
 int psim_kernel_times(psim_handle *h, const char **names, double *ms, uint64_t *launches, int cap);
 
 /* The cross-shard exchange since psim_create (G > 1: virtual shards or RCCL
@@ -587,6 +602,58 @@ int psim_get_comm_id(void *buf, size_t cap);
  * RCCL cannot (one GPU).  The W ranks are W host threads, each making the
  * same calls as RCCL ranks would (collective calls must be concurrent). */
 int psim_loopback_comm_id(void *buf, size_t cap);
+
+/* The host boundary: mixed clusters of simulated and outside nodes (DESIGN.md
+ * section 7, "The host boundary").  psim_host_comm_id writes the id
+ * (psim_comm_id_size() bytes: a magic value, lo, hi) of a host-exchange
+ * handle; PSIM_EINVAL for a null or short buffer or lo >= hi.  psim_create
+ * with it as cfg.comm_id (shard_world = 1, shard_rank = 0, n_shards <= 1,
+ * hi <= n_nodes, else PSIM_EINVAL; the full strategy: PSIM_EUNSUPPORTED)
+ * makes a handle that allocates and simulates exactly the nodes [lo, hi);
+ * every other id of [0, n_nodes) is outside, and the host speaks for it
+ * (lo = 0, hi = n_nodes: nothing is outside -- the boundary's one-party
+ * diagnostic).
+ *   Events follow the multi-rank rule: the host makes every event call on
+ * this handle, those that name outside nodes included (psim_join,
+ * psim_revive, psim_crash, psim_leave, psim_set_partition, psim_broadcast,
+ * the omission calls, the view-order tables), so an outside node's start,
+ * death, partition group and broadcast slots are known here as a remote
+ * rank's are.  psim_step, psim_leave_node, psim_get_histograms and
+ * psim_get_strategy_histograms answer PSIM_EUNSUPPORTED (the last three
+ * need a collective across the parties).
+ *   A round is three calls:
+ * psim_round_emit    applies the pending events and runs the owned nodes'
+ *     round up to its owner partition.  PSIM_ESTATE with a round open,
+ *     PSIM_EUNSUPPORTED on any other kind of handle (as the two below).
+ * psim_get_outbound  the open round's records addressed outside [lo, hi), 16
+ *     words each, in psim_wire_encode's layout (dst, src, type | ttl << 8 |
+ *     nex << 16, seq, a0..a3, ex[0..8)): first those for ids below lo, then
+ *     those for ids at or above hi, each side in ascending (src, seq) order.
+ *     recs == NULL or cap (in records) < *n: only *n is set.  May be called
+ *     again.  PSIM_ESTATE with no round open.
+ * psim_round_absorb  takes the n records outside nodes sent to owned nodes
+ *     this round, in any order: the result does not depend on it, every inbox
+ *     is built in the canonical (src, seq) order.  A host that decoded frames
+ *     (psim_wire_decode leaves seq = 0) numbers each source's records of the
+ *     round in their arrival order: seq = 0, 1, 2, ... per src.  Everything is
+ *     checked on the host before any device work, and a rejected call leaves
+ *     the handle unchanged, the round still open: a dst outside [lo, hi) or a
+ *     src inside it PSIM_ERANGE; a record psim_record_check refuses, its
+ *     code; a (src, seq) pair twice in the call PSIM_EINVAL.  On success the
+ *     records are routed together with the owned nodes' own, the next inboxes
+ *     built and the round closed; *stats (may be NULL) is this handle's share
+ *     of the round: the shares of all parties sum to the unsharded round's
+ *     stats in every field but `round`.  PSIM_ESTATE with no round open.
+ * While a round is open event calls still queue (for the next emit);
+ * psim_snapshot, psim_restore and the inspection getters (psim_get_nodes,
+ * psim_get_strategy_nodes, psim_get_member_bits, psim_get_delivery) answer
+ * PSIM_ESTATE.  Between rounds they behave as on a rank handle; a snapshot
+ * restores into a handle created with the same range.
+ * psim_get_exchange_stats counts outbound and absorbed records, 64 B each. */
+int psim_host_comm_id(void *buf, size_t cap, uint32_t lo, uint32_t hi);
+int psim_round_emit(psim_handle *h);
+int psim_get_outbound(psim_handle *h, uint32_t *recs, size_t cap, size_t *n);
+int psim_round_absorb(psim_handle *h, const uint32_t *recs, size_t n, psim_round_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -186,6 +186,14 @@ GPU_ONLY = {
     # (no oracle twin: the tests' reference is numpy over the oracle's views)
     "get_strategy_histograms": (C.c_int, [_H, C.POINTER(PsimStrategyHistograms)]),
 }
+# the host boundary (host-exchange handles: sim.HostSim, wire.check)
+HOST_BOUNDARY = {
+    "host_comm_id": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32]),
+    "round_emit": (C.c_int, [_H]),
+    "get_outbound": (C.c_int, [_H, _P32, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "round_absorb": (C.c_int, [_H, _P32, C.c_size_t, C.POINTER(PsimRoundStats)]),
+    "record_check": (C.c_int, [_P32, C.POINTER(PsimConfig)]),
+}
 
 
 def bind(lib, prefix, names):

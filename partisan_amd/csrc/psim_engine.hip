@@ -20,6 +20,9 @@
 //                    of the shard-ordered concatenation by dst
 //   stats    k_stats_tiles + k_stats_final (+ sum over shards / the ranks' all-reduce)
 // Ranks exchange through psim_comm.h: RCCL, or the loopback test vehicle.
+// A host-exchange handle (psim_host_comm_id) is one shard over a range of the
+// id space with the host in the ranks' place: its round is split at the
+// exchange (psim_round_emit .. psim_round_absorb; "the host boundary" below).
 // Grouping a (src, seq)-ordered stream -- or a concatenation ordered by
 // source shard -- by dst, each group in stream order, yields each inbox in
 // canonical (src, seq) order,
@@ -650,7 +653,7 @@ __global__ void __launch_bounds__(RB_STEP) k_bucket_fill(RouteIn in, uint32_t ns
 }
 
 // G > 1, sender side: this shard's outbox runs stably partitioned by owner
-// shard (owner = dst / per) straight into the send buffer in the wire format
+// shard (owner = Owner(dst): dst / per) straight into the send buffer in the wire format
 // (Wire: the heads of every owner, then the tails of every owner), so each
 // owner's records stay in (src, seq) order -- the receiver's route relies on
 // it.  Two passes; block blk takes the consecutive block steps [blk * spb,
@@ -675,9 +678,20 @@ __global__ void __launch_bounds__(RB_STEP) k_bucket_fill(RouteIn in, uint32_t ns
 // capacity is not written (k_owner_offsets aborts the round, code 3).  The
 // count pass's first blocks also sum the round's stats rows into tiles
 // (st.nt > 0: the stats travel in the headers instead of an all-reduce).
-template <bool WRITE>
+// Owner: the owner of a destination id -- OwnerDiv, the equal shards of the
+// virtual-shard and rank paths; OwnerRange, the three classes of a
+// host-exchange handle (below its range: 0, owned: 1, at or above: 2)
+struct OwnerDiv {
+    uint32_t per;
+    __device__ __forceinline__ uint32_t operator()(uint32_t d) const { return d / per; }
+};
+struct OwnerRange {
+    uint32_t lo, hi;
+    __device__ __forceinline__ uint32_t operator()(uint32_t d) const { return d < lo ? 0u : d < hi ? 1u : 2u; }
+};
+template <bool WRITE, class Owner = OwnerDiv>
 __global__ void __launch_bounds__(RB_STEP) k_owner_part(RouteIn in, uint32_t nsteps, uint32_t spb, uint32_t G,
-                                                        uint32_t per, uint32_t* hist,
+                                                        Owner owner, uint32_t* hist,
                                                         const uint32_t* __restrict__ off, Wire* __restrict__ out,
                                                         unsigned long long* mark, uint32_t capH, uint32_t capT,
                                                         const uint32_t* ctl, StatsIn st) {
@@ -730,7 +744,7 @@ __global__ void __launch_bounds__(RB_STEP) k_owner_part(RouteIn in, uint32_t nst
                 if (pre[mid] <= t) a = mid; else b = mid;
             }
             g = sbase[w][a] + (t - pre[a]);
-            return (in.okey[g] & KEY_DST_MASK) / per;
+            return owner(in.okey[g] & KEY_DST_MASK);
         };
         uint32_t cnt = 0, cntl = 0;                   // lane q: this wave's records / long records of owner q
         for (uint32_t t0 = 0; t0 < T; t0 += 64) {
@@ -890,6 +904,64 @@ __global__ void k_owner_offsets(const uint32_t* hoff, uint32_t nblk, uint32_t G,
     }
     __syncthreads();
     if (q < 128) xw[3 + q] = q == rank ? smh : q == 64 + rank ? smt : 0u;
+}
+
+// The host boundary (psim_round_emit / psim_get_outbound / psim_round_absorb):
+// one outside class's records between the wire format and dense 64-B records,
+// one record a lane -- 16-B loads and stores; the four of a lane stay inside
+// one 64-B half of a 128-B line, and neighbouring lanes take neighbouring
+// halves, so every line moved is used whole.
+constexpr uint32_t HX_BLK = 256;
+// k_host_export: n heads of one class (in (src, seq) order, k_owner_part) and
+// its tails -> out[0..n): head, then the tail (its index among the class's
+// tails is the head's word 7) or zeros; word 7 back to what the emitter
+// wrote -- 0 in a long record, kept in a short one (X-BOT's DisconnectNode);
+// pl: a pluggable handle's word 7 is a payload-arena slot, no part of the
+// message (the digest hashes it as 0): 0
+__global__ void __launch_bounds__(HX_BLK) k_host_export(const Wire* __restrict__ heads,
+                                                        const Wire* __restrict__ tails, uint32_t n,
+                                                        uint32_t n_tails, uint32_t pl, Msg* __restrict__ out) {
+    const uint32_t i = blockIdx.x * HX_BLK + threadIdx.x;
+    if (i >= n) return;
+    const uint4 h0 = heads[i].q[0];
+    uint4 h1 = heads[i].q[1];
+    uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0;
+    if (wire_long(h0.z)) {
+        if (h1.w < n_tails) { t0 = tails[h1.w].q[0]; t1 = tails[h1.w].q[1]; }
+        h1.w = 0;
+    }
+    if (pl) h1.w = 0;
+    uint4* o = reinterpret_cast<uint4*>(out + i);
+    o[0] = h0; o[1] = h1; o[2] = t0; o[3] = t1;
+}
+
+// k_host_import: n absorbed records of one class, sorted by (src, seq) ->
+// heads[0..n) and the long ones' tails in the same order, each long head's
+// tail index (among this class's tails) in its word 7 -- what k_owner_part
+// leaves for an owner, so the receive reads the class as one more source.
+// A wave takes 64 consecutive records: wbase[w] = the long records before
+// wave w's (counted by the host, which read every record to check it), the
+// rank inside the wave by ballot.
+__global__ void __launch_bounds__(HX_BLK) k_host_import(const Msg* __restrict__ rec, uint32_t n,
+                                                        const uint32_t* __restrict__ wbase, uint32_t n_tails,
+                                                        Wire* __restrict__ heads, Wire* __restrict__ tails) {
+    const uint32_t i = blockIdx.x * HX_BLK + threadIdx.x, l = threadIdx.x & 63;
+    const bool ok = i < n;
+    uint4 x0 = make_uint4(0, 0, 0, 0), x1 = x0, x2 = x0, x3 = x0;
+    if (ok) {
+        const uint4* sp = reinterpret_cast<const uint4*>(rec + i);
+        x0 = sp[0]; x1 = sp[1]; x2 = sp[2]; x3 = sp[3];
+    }
+    const bool lg = ok && wire_long(x0.z);
+    const uint64_t ml = __ballot(lg);                 // (every lane of the wave is here)
+    if (!ok) return;
+    if (lg) {
+        const uint32_t t = wbase[i >> 6] + (uint32_t)__popcll(ml & ((1ull << l) - 1ull));
+        x1.w = t;
+        if (t < n_tails) { tails[t].q[0] = x2; tails[t].q[1] = x3; }
+    }
+    heads[i].q[0] = x0;
+    heads[i].q[1] = x1;
 }
 
 
@@ -2278,9 +2350,9 @@ struct TmpBuf : DBuf<T> {
 };
 
 enum Kern { KT_EVENTS, KT_PREPARE, KT_CONSUME, KT_SCAN, KT_COMPACT, KT_SORT, KT_EXCHANGE, KT_GATHER,
-            KT_STATS, KT_N };
+            KT_STATS, KT_HOST_EXPORT, KT_HOST_IMPORT, KT_N };
 const char* kKernName[KT_N] = {"events", "prepare", "consume", "scan", "compact", "sort",
-                               "exchange", "gather", "stats"};
+                               "exchange", "gather", "stats", "k_host_export", "k_host_import"};
 
 inline uint32_t grid_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + BLK - 1) / BLK); }
 
@@ -2408,6 +2480,13 @@ struct Shard {
     uint64_t trace_tmax = 0, trace_mmax = 0;   // PSIM_TRACE_BOUND's high-water marks
 };
 
+// the events a handle holds for its next round (psim_handle's pend_* members)
+struct PendingEvents {
+    std::vector<uint32_t> crash, join, contact, lv_a, lv_t, b_root, b_msg;
+    std::vector<uint8_t> join_mark, part;
+    bool part_set = false, part_clear = false, faults_dirty = false;
+};
+
 }  // namespace
 
 struct psim_handle {
@@ -2436,6 +2515,16 @@ struct psim_handle {
     bool ranked = false;
     Comm* comm = nullptr;               // ranked: RCCL (or the loopback test vehicle), psim_comm.h
     DBuf<uint64_t> comm_cnt;            // RCCL: [send counts | recv counts]
+    // a host-exchange handle (cfg.comm_id from psim_host_comm_id): one shard,
+    // the range [lo, hi) of the id space; the host speaks for every other id.
+    // G = 3 owner classes (below, owned, at or above), the shard is class 1;
+    // a round is psim_round_emit .. psim_round_absorb (round_open between)
+    bool hosted = false, round_open = false;
+    std::vector<Msg> host_out, host_in; // the open round's outbound records; the absorbed ones, sorted
+    std::vector<uint32_t> host_wbase;   // k_host_import: the long records before each wave's
+    DBuf<Msg> hx_rec;                   // the dense records on the device (export, then import)
+    DBuf<uint32_t> hx_wbase;
+    PendingEvents open_ev;              // the events queued while the round is open (pending_swap)
     // the exchange since creation (psim_get_exchange_stats): records sent to
     // another shard, and their wire bytes (heads + tails)
     uint64_t x_records = 0, x_bytes = 0;
@@ -3264,11 +3353,22 @@ int phase_partition(psim_handle* h, Shard* s, bool fixed = false) {
     }
     {
         KTimer t(h, s, KT_SORT);
-        k_owner_part<false><<<nblk, RB_STEP, 0, s->stream>>>(in, nsteps, spb, G, h->per, s->hist.p, nullptr,
-                                                              nullptr, phase_end_mark(h, s), capH, capT, s->ctl.p, st);
+        // (a host-exchange handle: the three classes of its range)
+        const OwnerDiv div{h->per};
+        const OwnerRange rng{s->lo, s->lo + s->n};
+        if (h->hosted)
+            k_owner_part<false, OwnerRange><<<nblk, RB_STEP, 0, s->stream>>>(
+                in, nsteps, spb, G, rng, s->hist.p, nullptr, nullptr, phase_end_mark(h, s), capH, capT, s->ctl.p, st);
+        else
+            k_owner_part<false><<<nblk, RB_STEP, 0, s->stream>>>(in, nsteps, spb, G, div, s->hist.p, nullptr,
+                                                                  nullptr, phase_end_mark(h, s), capH, capT, s->ctl.p, st);
         TRY(scan_excl(s, s->hist.p, s->hoff.p, (uint32_t)nh));
-        k_owner_part<true><<<nblk, RB_STEP, 0, s->stream>>>(in, nsteps, spb, G, h->per, nullptr, s->hoff.p,
-                                                             s->sendbuf.p, nullptr, capH, capT, s->ctl.p, StatsIn{});
+        if (h->hosted)
+            k_owner_part<true, OwnerRange><<<nblk, RB_STEP, 0, s->stream>>>(
+                in, nsteps, spb, G, rng, nullptr, s->hoff.p, s->sendbuf.p, nullptr, capH, capT, s->ctl.p, StatsIn{});
+        else
+            k_owner_part<true><<<nblk, RB_STEP, 0, s->stream>>>(in, nsteps, spb, G, div, nullptr, s->hoff.p,
+                                                                 s->sendbuf.p, nullptr, capH, capT, s->ctl.p, StatsIn{});
         k_owner_offsets<<<1, OO_THREADS, 0, s->stream>>>(s->hoff.p, nblk, G, s->d_off.p, rccl ? h->comm_cnt.p : nullptr,
                                                   rccl ? s->stat_out.p + STAT_OUT_X : nullptr, capH, capT, s->ctl.p,
                                                   (uint32_t)h->round, s->idx, s->sendbuf.p, st);
@@ -3421,7 +3521,7 @@ int exchange_rccl(psim_handle* h) {
 // A sender whose owner count passed a capacity aborted the round
 // (k_owner_offsets, code 3) and every rank redoes it exactly
 // (run_batch_ranked).  The padding crosses the link too: a capacity is the
-// largest per-owner count seen so far, 1.25x (xcaps_update).
+// largest per-owner count seen so far, 1.5x (xcaps_set).
 int exchange_fixed(psim_handle* h) {
     Shard* s = h->shards[0];
     const uint32_t G = h->G, capT = s->xcap_t;
@@ -3520,7 +3620,11 @@ void bcast_slots(psim_handle* h, RoundCtl& ctl) {
 // from_partition: the node-round phase ran already (a rank's redo of an
 // aborted batch round, run_batch_ranked): the round goes on from its owner
 // partition, over the outbox that phase left.
-int run_round(psim_handle* h, uint64_t* st, bool events_applied = false, bool from_partition = false) {
+// round_front: the pending events, the prepare and the node-round phase;
+// round_back: after the route, the round's end and its stats into st[NST].
+// (A host-exchange handle runs the two from different calls: host_emit,
+// host_absorb.)
+int round_front(psim_handle* h, bool events_applied, bool from_partition) {
     RoundCtl ctl;
     ctl.crashes = !h->pend_crash.empty();
     if (!events_applied) bcast_slots(h, ctl);
@@ -3542,6 +3646,13 @@ int run_round(psim_handle* h, uint64_t* st, bool events_applied = false, bool fr
         return PSIM_ENOMEM;
     }
     for (size_t i = 0; i < h->shards.size() && !from_partition; i++) TRY(phase_consume(h, h->shards[i], args[i]));
+    return PSIM_OK;
+}
+
+int round_back(psim_handle* h, uint64_t* st);
+
+int run_round(psim_handle* h, uint64_t* st, bool events_applied = false, bool from_partition = false) {
+    TRY(round_front(h, events_applied, from_partition));
     if (local_route(h)) {
         TRY(phase_route_local(h, h->shards[0]));
     } else {
@@ -3549,6 +3660,10 @@ int run_round(psim_handle* h, uint64_t* st, bool events_applied = false, bool fr
         if (h->ranked) TRY(exchange_rccl(h));
         else TRY(exchange_local(h));
     }
+    return round_back(h, st);
+}
+
+int round_back(psim_handle* h, uint64_t* st) {
     for (Shard* s : h->shards) {
         TRY(phase_stats(h, s, h->pend_crash));
         if (!h->pend_b_root.empty())        // this round's origins are spent
@@ -3663,6 +3778,125 @@ void fill_stats(const uint64_t* s, uint64_t round, psim_round_stats* o) {
     o->overflow = s[ST_OVF]; o->digest = s[ST_DIGEST]; o->state_bytes = s[ST_BYTES];
     for (int k = 0; k < PSIM_OVF_NKINDS; k++) o->overflow_by[k] = s[ST_OVF_BY + k];
     o->omitted = s[ST_OMIT];
+}
+
+// ------------------------------------------------- the host boundary --
+// A host-exchange handle's round ("The host boundary").
+// The shard is owner class 1 of G = 3: the owner partition leaves the two
+// outside classes' records in the send buffer, k_host_export makes dense
+// records of them for the host; the absorbed records come back through
+// k_host_import as the receive's sources 0 and 2, beside the handle's own
+// class 1 (a device copy, as exchange_rccl's for a rank's own records).
+void pending_swap(psim_handle* h, PendingEvents& e) {
+    std::swap(h->pend_crash, e.crash); std::swap(h->pend_join, e.join); std::swap(h->pend_contact, e.contact);
+    std::swap(h->pend_join_mark, e.join_mark);
+    std::swap(h->pend_lv_a, e.lv_a); std::swap(h->pend_lv_t, e.lv_t);
+    std::swap(h->pend_part, e.part);
+    std::swap(h->pend_part_set, e.part_set); std::swap(h->pend_part_clear, e.part_clear);
+    std::swap(h->pend_b_root, e.b_root); std::swap(h->pend_b_msg, e.b_msg);
+    std::swap(h->faults_dirty, e.faults_dirty);
+}
+
+int host_emit(psim_handle* h) {
+    Shard* s = h->shards[0];
+    const uint32_t G = h->G;
+    for (int k = 0; k < KT_N; k++) { h->kt_ms[k] = 0; h->kt_n[k] = 0; }
+    TRY(round_front(h, false, false));
+    TRY(phase_partition(h, s));                       // (waits: soff, scnt, lcnt are on the host)
+    const uint64_t nout = s->scnt[0] + s->scnt[2];
+    h->host_out.resize(nout);
+    if (nout) {
+        TRY(h->hx_rec.ensure(nout));
+        {
+            KTimer t(h, s, KT_HOST_EXPORT);
+            uint64_t at = 0;
+            for (uint32_t q = 0; q < G; q += 2) {     // below, then at or above
+                const uint32_t c = (uint32_t)s->scnt[q];
+                if (c)
+                    k_host_export<<<(c + HX_BLK - 1) / HX_BLK, HX_BLK, 0, s->stream>>>(
+                        s->sendbuf.p + s->soff[q], s->sendbuf.p + s->soff[G + q], c, (uint32_t)s->lcnt[q],
+                        h->cfg.manager == PSIM_MANAGER_PLUGGABLE ? 1u : 0u, h->hx_rec.p + at);
+                at += c;
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(h->host_out.data(), h->hx_rec.p, nout * sizeof(Msg), hipMemcpyDeviceToHost, s->stream));
+        TRY(stream_wait(s));
+    }
+    h->x_records += nout;
+    h->x_bytes += nout * sizeof(Msg);
+    // the round's events stay aside until its absorb (k_uncrash, the spent
+    // origins); calls made meanwhile queue for the next emit
+    h->open_ev = PendingEvents{};
+    pending_swap(h, h->open_ev);
+    h->round_open = true;
+    return PSIM_OK;
+}
+
+// `in`: the absorbed records, checked, sorted by (src, seq); nb of them from
+// below the range
+int host_absorb(psim_handle* h, size_t nb, uint64_t* st) {
+    Shard* s = h->shards[0];
+    const uint32_t G = h->G;
+    const size_t n = h->host_in.size(), side[2] = {nb, n - nb};
+    // per side the long records before each wave of 64 (k_host_import)
+    const size_t nw[2] = {(side[0] + 63) / 64, (side[1] + 63) / 64};
+    h->host_wbase.assign(nw[0] + nw[1] + 1, 0);
+    std::vector<uint64_t> hc(G), lc(G);
+    for (int k = 0; k < 2; k++) {
+        const Msg* r = h->host_in.data() + (k ? nb : 0);
+        uint32_t* wb = h->host_wbase.data() + (k ? nw[0] : 0);
+        uint32_t lg = 0;
+        for (size_t i = 0; i < side[k]; i++) {
+            if ((i & 63) == 0) wb[i >> 6] = lg;
+            lg += wire_long(r[i].tt) ? 1u : 0u;
+        }
+        hc[2 * k] = side[k];
+        lc[2 * k] = lg;
+    }
+    hc[1] = s->scnt[1];
+    lc[1] = s->lcnt[1];
+    const uint64_t oh[3] = {0, hc[0], hc[0] + hc[1]}, ot[3] = {0, lc[0], lc[0] + lc[1]};
+    TRY(s->recvh.ensure(oh[2] + hc[2] + 1));
+    TRY(s->recvt.ensure(ot[2] + lc[2] + 1));
+    if (n) {
+        TRY(h->hx_rec.ensure(n));
+        TRY(h->hx_wbase.ensure(h->host_wbase.size()));
+        // (host_in and host_wbase live until the next absorb; the round's end waits for the stream)
+        HIP_TRY(hipMemcpyAsync(h->hx_rec.p, h->host_in.data(), n * sizeof(Msg), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(h->hx_wbase.p, h->host_wbase.data(), h->host_wbase.size() * 4, hipMemcpyHostToDevice,
+                               s->stream));
+        KTimer t(h, s, KT_HOST_IMPORT);
+        for (int k = 0; k < 2; k++) {
+            const uint32_t c = (uint32_t)side[k];
+            if (c)
+                k_host_import<<<(c + HX_BLK - 1) / HX_BLK, HX_BLK, 0, s->stream>>>(
+                    h->hx_rec.p + (k ? nb : 0), c, h->hx_wbase.p + (k ? nw[0] : 0), (uint32_t)lc[2 * k],
+                    s->recvh.p + oh[2 * k], s->recvt.p + ot[2 * k]);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        KTimer t(h, s, KT_EXCHANGE);
+        if (hc[1])
+            HIP_TRY(hipMemcpyAsync(s->recvh.p + oh[1], s->sendbuf.p + s->soff[1], hc[1] * sizeof(Wire),
+                                   hipMemcpyDeviceToDevice, s->stream));
+        if (lc[1])
+            HIP_TRY(hipMemcpyAsync(s->recvt.p + ot[1], s->sendbuf.p + s->soff[G + 1], lc[1] * sizeof(Wire),
+                                   hipMemcpyDeviceToDevice, s->stream));
+    }
+    h->x_records += n;
+    h->x_bytes += n * sizeof(Msg);
+    TRY(phase_receive(h, s, hc, lc));
+    // the round's own events back in place for its end; the ones queued since
+    // the emit (and a stop this round found) are the next round's
+    pending_swap(h, h->open_ev);
+    TRY(round_back(h, st));
+    h->open_ev.crash.insert(h->open_ev.crash.begin(), h->pend_crash.begin(), h->pend_crash.end());
+    pending_swap(h, h->open_ev);
+    h->open_ev = PendingEvents{};
+    h->round_open = false;
+    return PSIM_OK;
 }
 
 // Whether psim_step may run its rounds as batches (run_batch): one RCCL-free
@@ -4123,6 +4357,15 @@ void shard_free(Shard* s) {
     delete s;
 }
 
+// a host-exchange id (psim_host_comm_id): a magic value, then lo and hi
+const char kHostMagic[8] = {'P', 'S', 'I', 'M', 'H', 'O', 'S', 'T'};
+bool host_id_range(const void* id, uint32_t* lo, uint32_t* hi) {
+    if (!id || memcmp(id, kHostMagic, sizeof kHostMagic) != 0) return false;
+    memcpy(lo, (const char*)id + sizeof kHostMagic, 4);
+    memcpy(hi, (const char*)id + sizeof kHostMagic + 4, 4);
+    return *lo < *hi;
+}
+
 }  // namespace
 
 // ================================================================ C ABI ==
@@ -4188,10 +4431,15 @@ int psim_create(const psim_config* cfg, psim_handle** out) {
     uint32_t local = std::max<uint32_t>(cfg->n_shards, 1);
     // the rank path: world > 1, or one rank with a communicator id (the
     // 1-GPU diagnostic of the RCCL path)
-    const bool ranked = world > 1 || cfg->comm_id != nullptr;
+    // a host-exchange handle (an id from psim_host_comm_id): one shard, the
+    // range [lo, hi); three owner classes -- below, owned, at or above
+    uint32_t host_lo = 0, host_hi = 0;
+    const bool hosted = host_id_range(cfg->comm_id, &host_lo, &host_hi);
+    if (hosted && (world != 1 || cfg->shard_rank != 0 || local != 1 || host_hi > cfg->n_nodes)) return PSIM_EINVAL;
+    const bool ranked = !hosted && (world > 1 || cfg->comm_id != nullptr);
     if (ranked && (local != 1 || !cfg->comm_id || cfg->shard_rank >= world)) return PSIM_EINVAL;
-    uint32_t G = ranked ? world : local;
-    if (G > 64 || G > cfg->n_nodes) return PSIM_EINVAL;
+    uint32_t G = hosted ? 3 : ranked ? world : local;
+    if (!hosted && (G > 64 || G > cfg->n_nodes)) return PSIM_EINVAL;
     if (full && G > 1) return PSIM_EUNSUPPORTED;      // gossip payloads are shard-local
     psim_handle* h = new (std::nothrow) psim_handle();
     if (!h) return PSIM_ENOMEM;
@@ -4206,6 +4454,7 @@ int psim_create(const psim_config* cfg, psim_handle** out) {
     h->per = (h->N + G - 1) / G;
     h->world = (int)world;
     h->ranked = ranked;
+    h->hosted = hosted;
     h->rank = (int)cfg->shard_rank;
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) { delete h; return PSIM_EDEVICE; }
@@ -4255,11 +4504,13 @@ int psim_create(const psim_config* cfg, psim_handle** out) {
     h->device = dev;
     for (uint32_t g = 0; g < G; g++) {
         if (ranked && g != cfg->shard_rank) continue;
+        if (hosted && g != 1) continue;
         Shard* s = new (std::nothrow) Shard();
         if (!s) { psim_destroy(h); return PSIM_ENOMEM; }
         s->idx = g;
         s->lo = std::min<uint32_t>(g * h->per, h->N);
         s->n = std::min<uint32_t>(h->N, s->lo + h->per) - s->lo;
+        if (hosted) { s->lo = host_lo; s->n = host_hi - host_lo; }
         h->shards.push_back(s);
         int rc = shard_alloc(h, s);
         if (!rc && hipMemcpy(s->slots.p, h->slot_tab, sizeof h->slot_tab, hipMemcpyHostToDevice) != hipSuccess)
@@ -4295,6 +4546,7 @@ void psim_destroy(psim_handle* h) {
     for (Shard* s : h->shards) shard_free(s);
     h->shards.clear();
     h->comm_cnt.release();
+    h->hx_rec.release(); h->hx_wbase.release();
     delete h->comm;
     delete h;
 }
@@ -4363,6 +4615,7 @@ int psim_leave(psim_handle* h, const uint32_t* nodes, size_t n) {
 int psim_leave_node(psim_handle* h, const uint32_t* actors, const uint32_t* targets, size_t n) {
     if (!h || (n && (!actors || !targets))) return PSIM_EINVAL;
     if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE) return PSIM_EUNSUPPORTED;
+    if (h->hosted) return PSIM_EUNSUPPORTED;          // (the stop list needs a gather across the parties)
     for (size_t i = 0; i < n; i++) {
         if (actors[i] >= h->N || targets[i] >= h->N) return PSIM_ERANGE;
         for (uint32_t a : h->pend_lv_a) if (a == actors[i]) return PSIM_EINVAL;
@@ -4519,6 +4772,7 @@ int grow_outx(Shard* s) {
 
 int psim_step(psim_handle* h, uint32_t n_rounds, psim_round_stats* stats) {
     if (!h) return PSIM_EINVAL;
+    if (h->hosted) return PSIM_EUNSUPPORTED;          // (psim_round_emit .. psim_round_absorb drive the rounds)
     if (h->failed) return PSIM_ESTATE;
     if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
     for (int k = 0; k < KT_N; k++) { h->kt_ms[k] = 0; h->kt_n[k] = 0; }
@@ -4570,6 +4824,77 @@ int psim_step(psim_handle* h, uint32_t n_rounds, psim_round_stats* stats) {
                              (unsigned long long)s->trace_tmax, s->outbox.n, (unsigned long long)s->trace_mmax,
                              (unsigned long long)s->rcap);
             }
+    return PSIM_OK;
+}
+
+// ---- the host boundary: a round of a host-exchange handle (host_emit, host_absorb)
+int psim_round_emit(psim_handle* h) {
+    if (!h) return PSIM_EINVAL;
+    if (!h->hosted) return PSIM_EUNSUPPORTED;
+    if (h->failed || h->round_open) return PSIM_ESTATE;
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    const int rc = host_emit(h);
+    if (rc) h->failed = true;
+    return rc;
+}
+
+int psim_get_outbound(psim_handle* h, uint32_t* recs, size_t cap, size_t* n) {
+    if (!h || !n) return PSIM_EINVAL;
+    if (!h->hosted) return PSIM_EUNSUPPORTED;
+    if (!h->round_open) return PSIM_ESTATE;
+    *n = h->host_out.size();
+    if (recs && cap >= *n && *n) memcpy(recs, h->host_out.data(), *n * sizeof(Msg));
+    return PSIM_OK;
+}
+
+int psim_round_absorb(psim_handle* h, const uint32_t* recs, size_t n, psim_round_stats* stats) {
+    if (!h || (n && !recs)) return PSIM_EINVAL;
+    if (!h->hosted) return PSIM_EUNSUPPORTED;
+    if (h->failed || !h->round_open) return PSIM_ESTATE;
+    Shard* s = h->shards[0];
+    const uint32_t lo = s->lo, hi = s->lo + s->n;
+    // everything is checked here, before any device work: a rejected call
+    // leaves the handle as it was, the round still open
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t* r = recs + i * 16;
+        if (r[0] < lo || r[0] >= hi || (r[1] >= lo && r[1] < hi)) return PSIM_ERANGE;
+        const int rc = psim_record_check(r, &h->cfg);
+        if (rc) return rc;
+    }
+    // the canonical (src, seq) order, whatever order they came in
+    std::vector<uint32_t> ord(n);
+    for (size_t i = 0; i < n; i++) ord[i] = (uint32_t)i;
+    std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
+        const uint32_t *x = recs + (size_t)a * 16, *y = recs + (size_t)b * 16;
+        return x[1] != y[1] ? x[1] < y[1] : x[3] < y[3];
+    });
+    for (size_t i = 1; i < n; i++) {
+        const uint32_t *x = recs + (size_t)ord[i - 1] * 16, *y = recs + (size_t)ord[i] * 16;
+        if (x[1] == y[1] && x[3] == y[3]) return PSIM_EINVAL;
+    }
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    h->host_in.resize(n);
+    size_t nb = 0;
+    for (size_t i = 0; i < n; i++) {
+        memcpy(&h->host_in[i], recs + (size_t)ord[i] * 16, sizeof(Msg));
+        nb += h->host_in[i].src < lo ? 1u : 0u;
+    }
+    uint64_t st[NST];
+    const uint64_t r = h->round;
+    int rc = host_absorb(h, nb, st);
+    if (!rc) rc = grow_outx(s);
+    if (rc) { h->failed = true; return rc; }
+    if (stats) fill_stats(st, r, stats);
+    if (h->cfg.strict && st[ST_OVF]) return PSIM_ECAPACITY;
+    return PSIM_OK;
+}
+
+int psim_host_comm_id(void* buf, size_t cap, uint32_t lo, uint32_t hi) {
+    if (!buf || cap < sizeof(ncclUniqueId) || lo >= hi) return PSIM_EINVAL;
+    memset(buf, 0, sizeof(ncclUniqueId));
+    memcpy(buf, kHostMagic, sizeof kHostMagic);
+    memcpy((char*)buf + sizeof kHostMagic, &lo, 4);
+    memcpy((char*)buf + sizeof kHostMagic + 4, &hi, 4);
     return PSIM_OK;
 }
 
@@ -4671,6 +4996,7 @@ static int get_shard_nodes(Shard* s, uint32_t first, uint32_t count, psim_node_v
 // nodes [first, first+count): every node must be owned by a shard of this process
 int psim_get_nodes(psim_handle* h, uint32_t first, uint32_t count, psim_node_view* out) {
     if (!h || (count && !out)) return PSIM_EINVAL;
+    if (h->round_open) return PSIM_ESTATE;
     if ((uint64_t)first + count > h->N) return PSIM_ERANGE;
     if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
     uint32_t done = 0;
@@ -4710,7 +5036,7 @@ static Shard* owner_of(psim_handle* h, uint32_t id) {
 
 int psim_get_strategy_nodes(psim_handle* h, uint32_t first, uint32_t count, psim_strategy_view* out) {
     if (!h || (count && !out)) return PSIM_EINVAL;
-    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE) return PSIM_ESTATE;
+    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE || h->round_open) return PSIM_ESTATE;
     if ((uint64_t)first + count > h->N) return PSIM_ERANGE;
     if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
     const bool full = h->cfg.strategy == PSIM_STRATEGY_FULL;
@@ -4773,7 +5099,8 @@ int psim_get_strategy_nodes(psim_handle* h, uint32_t first, uint32_t count, psim
 
 int psim_get_member_bits(psim_handle* h, uint32_t node, uint32_t* words, size_t n_words) {
     if (!h || !words) return PSIM_EINVAL;
-    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE || h->cfg.strategy != PSIM_STRATEGY_FULL) return PSIM_ESTATE;
+    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE || h->cfg.strategy != PSIM_STRATEGY_FULL || h->round_open)
+        return PSIM_ESTATE;
     if (node >= h->N) return PSIM_ERANGE;
     const uint32_t W = (h->N + 31) / 32;
     if (n_words < W) return PSIM_EINVAL;
@@ -4792,6 +5119,7 @@ int psim_get_member_bits(psim_handle* h, uint32_t node, uint32_t* words, size_t 
 int psim_get_delivery(psim_handle* h, uint32_t first, uint32_t count, uint8_t* have, uint32_t* round,
                       uint32_t* hop) {
     if (!h || (count && (!have || !round || !hop))) return PSIM_EINVAL;
+    if (h->round_open) return PSIM_ESTATE;
     if ((uint64_t)first + count > h->N) return PSIM_ERANGE;
     if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
     const uint64_t bit = h->tracked_msg == PSIM_NONE ? 0ull : 1ull << (h->tracked_msg % PSIM_MSG_SLOTS);
@@ -4839,7 +5167,7 @@ static int cc_run(const uint32_t* off, const uint8_t* rn, const uint32_t* adj, c
 
 int psim_get_histograms(psim_handle* h, psim_histograms* out) {
     if (!h || !out) return PSIM_EINVAL;
-    if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE) return PSIM_EUNSUPPORTED;
+    if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE || h->hosted) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
     if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
     memset(out, 0, sizeof *out);
     Shard* s0 = h->shards[0];
@@ -4940,7 +5268,7 @@ static int strategy_hist_full(psim_handle* h, psim_strategy_histograms* out) {
 
 int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) {
     if (!h || !out) return PSIM_EINVAL;
-    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE) return PSIM_EUNSUPPORTED;
+    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE || h->hosted) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
     if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
     memset(out, 0, sizeof *out);
     for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
@@ -5062,6 +5390,7 @@ static std::vector<Section> snap_sections(psim_handle* h, Shard* s, const ShardH
 
 int psim_snapshot(psim_handle* h, void* buf, size_t cap, size_t* need) {
     if (!h || !need) return PSIM_EINVAL;
+    if (h->round_open) return PSIM_ESTATE;
     if (!h->pend_crash.empty() || !h->pend_join.empty() || !h->pend_lv_a.empty() || h->pend_part_set || h->pend_part_clear ||
         !h->pend_b_root.empty() || h->faults || h->faults_dirty)   // (faults: host state, not snapshotted)
         return PSIM_ESTATE;
@@ -5101,6 +5430,7 @@ int psim_snapshot(psim_handle* h, void* buf, size_t cap, size_t* need) {
 
 int psim_restore(psim_handle* h, const void* buf, size_t size) {
     if (!h || !buf || size < sizeof(SnapHead)) return PSIM_EINVAL;
+    if (h->round_open && !h->failed) return PSIM_ESTATE;   // (a failed absorb left it open: a restore closes it)
     if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
     const char* o = static_cast<const char*>(buf);
     const char* end = o + size;
@@ -5185,6 +5515,8 @@ int psim_restore(psim_handle* h, const void* buf, size_t size) {
     HIP_TRY(hipDeviceSynchronize());
     // back on a round boundary: a handle a failed step poisoned runs again
     h->failed = false;
+    h->round_open = false;
+    h->open_ev = PendingEvents{};
     h->pend_crash.clear(); h->pend_join.clear(); h->pend_contact.clear();
     h->pend_lv_a.clear(); h->pend_lv_t.clear();
     h->pend_join_mark.assign(h->pend_join_mark.size(), 0);

@@ -459,9 +459,68 @@ bool names_of(const psim_wire_names* w, Names& nm) {
     return true;
 }
 
+// ------------------------------------------------------- record check --
+// The words of a record its receiving handler reads as node ids, beside dst,
+// src and ex[0 .. nex): the table above, by another reading -- what the
+// handlers index device tables with (psim_consume.hip, psim_strategy.hip).
+enum : uint32_t {
+    ID_A0 = 1, ID_A1 = 2, ID_A2 = 4, ID_A3 = 8,
+    ID_A2_IDENT = 16,       // a2 is a Plumtree identity: PSIM_MAP_BIT allowed
+    ID_A2_NONE = 32,        // ... and may be PSIM_NONE (an IHAVE of a retired id)
+    ID_A3_NONE = 64,        // a3 may be PSIM_NONE (X-BOT's undefined DisconnectNode)
+    ID_UNKNOWN = 0x80000000u
+};
+
+uint32_t id_words(const psim_config& c, uint32_t type) {
+    if (c.manager == PSIM_MANAGER_PLUGGABLE) {
+        const bool full = c.strategy == PSIM_STRATEGY_FULL;
+        switch (type) {
+        case PSIM_PL_HELLO: return 0;
+        // (the full strategy's STATE and GOSSIP carry a payload-arena slot in
+        // word 7: shard-local, no record of them crosses a boundary)
+        case PSIM_PL_STATE: return full ? ID_UNKNOWN : 0;
+        case PSIM_PL_FWD_SUB: case PSIM_PL_PING: case PSIM_PL_KEEP_SUB: case PSIM_PL_REMOVE_SUB:
+        case PSIM_PL_BOOT_REMOVE: return full ? ID_UNKNOWN : ID_A0;
+        default: return ID_UNKNOWN;
+        }
+    }
+    switch (type) {
+    case PSIM_MSG_FORWARD_JOIN: return ID_A0;
+    case PSIM_MSG_JOIN: case PSIM_MSG_NEIGHBOR: case PSIM_MSG_DISCONNECT: case PSIM_MSG_NEIGHBOR_REQUEST:
+    case PSIM_MSG_NEIGHBOR_ACCEPTED: case PSIM_MSG_NEIGHBOR_REJECTED: case PSIM_MSG_SHUFFLE:
+    case PSIM_MSG_SHUFFLE_REPLY: return 0;
+    case PSIM_MSG_PT_IHAVE: return ID_A2 | ID_A2_IDENT | ID_A2_NONE;
+    case PSIM_MSG_PT_BROADCAST: case PSIM_MSG_PT_PRUNE: case PSIM_MSG_PT_IGNORED_IHAVE: case PSIM_MSG_PT_GRAFT:
+        return ID_A2 | ID_A2_IDENT;
+    case PSIM_MSG_XBOT_OPTIMIZATION: case PSIM_MSG_XBOT_OPTIMIZATION_REPLY: case PSIM_MSG_XBOT_REPLACE:
+    case PSIM_MSG_XBOT_REPLACE_REPLY: case PSIM_MSG_XBOT_SWITCH: case PSIM_MSG_XBOT_SWITCH_REPLY:
+        return c.manager == PSIM_MANAGER_XBOT ? ID_A0 | ID_A1 | ID_A2 | ID_A3 | ID_A3_NONE : ID_UNKNOWN;
+    default: return ID_UNKNOWN;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int psim_record_check(const uint32_t rec[16], const psim_config* cfg) {
+    if (!rec || !cfg || cfg->manager > PSIM_MANAGER_XBOT) return PSIM_EINVAL;
+    const uint32_t type = rec[2] & 0xFF, nex = (rec[2] >> 16) & 0xFF, n = cfg->n_nodes;
+    const uint32_t w = id_words(*cfg, type);
+    if (w == ID_UNKNOWN || nex > PSIM_EXCHANGE_CAP || (rec[2] >> 24)) return PSIM_EINVAL;
+    if (rec[0] >= n || rec[1] >= n) return PSIM_ERANGE;
+    for (uint32_t k = 0; k < nex; k++)
+        if (rec[8 + k] >= n) return PSIM_ERANGE;
+    if ((w & ID_A0) && rec[4] >= n) return PSIM_ERANGE;
+    if ((w & ID_A1) && rec[5] >= n) return PSIM_ERANGE;
+    if (w & ID_A2) {
+        const uint32_t a2 = rec[6];
+        if (!((w & ID_A2_NONE) && a2 == PSIM_NONE) && ((w & ID_A2_IDENT) ? a2 & ~PSIM_MAP_BIT : a2) >= n)
+            return PSIM_ERANGE;
+    }
+    if ((w & ID_A3) && !((w & ID_A3_NONE) && rec[7] == PSIM_NONE) && rec[7] >= n) return PSIM_ERANGE;
+    return PSIM_OK;
+}
 
 int psim_wire_encode(const uint32_t rec[16], const psim_wire_names* names, uint8_t* buf, size_t cap, size_t* len) {
     Names nm;

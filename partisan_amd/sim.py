@@ -317,6 +317,21 @@ def loopback_comm_id():
     return buf.raw
 
 
+def host_comm_id(lo, hi):
+    """The id of a host-exchange handle that owns the ids [lo, hi)
+    (psim_host_comm_id); HostSim passes it as cfg.comm_id."""
+    from . import _lib
+
+    lib = _lib.load()
+    extra = _abi.bind(lib, "psim_", _abi.GPU_ONLY)
+    n = extra["comm_id_size"]()
+    buf = C.create_string_buffer(n)
+    rc = _abi.bind(lib, "psim_", _abi.HOST_BOUNDARY)["host_comm_id"](buf, n, lo, hi)
+    if rc != 0:
+        raise SimError(f"host_comm_id: {extra['strerror'](rc).decode()}")
+    return buf.raw
+
+
 class Simulator(_Driver):
     """MI355X simulator handle (HIP library; fails loudly without it).
 
@@ -392,4 +407,51 @@ class Simulator(_Driver):
         return {names[i].decode(): (ms[i], launches[i]) for i in range(k)}
 
 
-__all__ = ["Simulator", "SimError", "default_config", "comm_id", "NONE"]
+class HostSim(Simulator):
+    """A host-exchange handle: the engine simulates the ids [lo, hi) of
+    cfg.n_nodes and the host speaks for every other id (real partisan nodes,
+    or another simulator).  Every event call is made here too, for outside
+    nodes as well.  A round is emit() -> outbound() -> absorb(records);
+    step() raises SimError."""
+
+    def __init__(self, cfg, lo, hi):
+        from . import _lib
+
+        self.lo, self.hi = lo, hi
+        self._host = _abi.bind(_lib.load(), "psim_", _abi.HOST_BOUNDARY)
+        super().__init__(cfg, comm=host_comm_id(lo, hi))
+
+    def emit(self):
+        """Apply the pending events and run the owned nodes' round."""
+        self._check(self._host["round_emit"](self._h), "round_emit")
+
+    def outbound(self):
+        """The open round's records for outside nodes, an (n, 16) uint32
+        array in the wire codec's layout: ids below lo first, then ids at or
+        above hi, each side in (src, seq) order."""
+        n = C.c_size_t()
+        self._check(self._host["get_outbound"](self._h, None, 0, C.byref(n)), "get_outbound")
+        out = np.zeros((n.value, 16), np.uint32)
+        self._check(self._host["get_outbound"](self._h, _abi.u32p(out), n.value, C.byref(n)), "get_outbound")
+        return out
+
+    def absorb(self, recs):
+        """Close the round with the records outside nodes sent to owned
+        nodes, in any order; returns this handle's stats row of the round."""
+        r = np.ascontiguousarray(recs, np.uint32).reshape(-1, 16)
+        st = np.zeros(1, _abi.STATS_DTYPE)
+        self._check(self._host["round_absorb"](self._h, _abi.u32p(r), r.shape[0],
+                                                st.ctypes.data_as(C.POINTER(_abi.PsimRoundStats))), "round_absorb")
+        return st
+
+    def nodes(self, first=None, count=None):
+        """Views of owned nodes (default: the whole owned range)."""
+        first = self.lo if first is None else first
+        return super().nodes(first, self.hi - first if count is None else count)
+
+    def strategy_nodes(self, first=None, count=None):
+        first = self.lo if first is None else first
+        return super().strategy_nodes(first, self.hi - first if count is None else count)
+
+
+__all__ = ["Simulator", "HostSim", "SimError", "default_config", "comm_id", "host_comm_id", "NONE"]

@@ -62,3 +62,16 @@ def decode(data, nm, dst):
     if rc != 0:
         raise WireError("not a partisan message frame")
     return r, used.value
+
+
+def check(rec, cfg):
+    """psim_record_check: 0 if the record may enter a handle of `cfg`, else
+    the negative PSIM_E* code (-1 EINVAL: a type the manager's handlers do
+    not receive, or nex past the exchange capacity; -5 ERANGE: a node id at
+    or past cfg.n_nodes)."""
+    from . import _abi
+
+    fn = _abi.bind(_lib.load(), "psim_", {"record_check": _abi.HOST_BOUNDARY["record_check"]})["record_check"]
+    r = np.ascontiguousarray(rec, np.uint32)
+    assert r.size == 16
+    return fn(r.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(cfg))
