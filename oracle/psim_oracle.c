@@ -107,6 +107,7 @@ struct psim_handle {
     uint8_t *part, *crashed_now;
     uint64_t round;
     msgvec inbox, out;              /* inbox sorted by (dst, src, seq) */
+    int oom;                        /* a round buffer could not grow: steps fail from then on */
     size_t *in_beg;                 /* N+1 offsets into inbox */
     /* pending events */
     uint32_t *pend_crash; size_t pend_crash_n, pend_crash_cap;
@@ -359,12 +360,16 @@ static uint64_t msg_hash(const omsg *m) {
     return h;
 }
 
-static void vec_push(msgvec *v, const omsg *m) {
+/* 0: the vector could not grow (it keeps what it holds; *m is not added) */
+static int vec_push(msgvec *v, const omsg *m) {
     if (v->n == v->cap) {
-        v->cap = v->cap ? v->cap * 2 : 1024;
-        v->v = (omsg *)realloc(v->v, v->cap * sizeof(omsg));
+        size_t cap = v->cap ? v->cap * 2 : 1024;
+        omsg *p = (omsg *)realloc(v->v, cap * sizeof(omsg));
+        if (!p) return 0;
+        v->v = p; v->cap = cap;
     }
     v->v[v->n++] = *m;
+    return 1;
 }
 
 static void emit4(ctx *c, uint32_t dst, uint32_t type, uint32_t ttl, uint32_t a0, uint32_t a1,
@@ -375,7 +380,9 @@ static void emit4(ctx *c, uint32_t dst, uint32_t type, uint32_t ttl, uint32_t a0
     m.type = type; m.ttl = ttl; m.nex = nex;
     m.a0 = a0; m.a1 = a1; m.a2 = a2; m.a3 = a3;
     for (uint32_t i = 0; i < nex; i++) m.ex[i] = ex[i];
-    vec_push(&c->h->out, &m);
+    /* (once the outbox could not grow the step fails, PSIM_ENOMEM: the rest of
+       the round's records are dropped without asking again) */
+    if (!c->h->oom && !vec_push(&c->h->out, &m)) c->h->oom = 1;
     c->h->st->emitted[type]++;
     c->h->st->digest += msg_hash(&m);
 }
@@ -1344,9 +1351,12 @@ static uint32_t full_nth(struct psim_handle *h, const uint32_t *b, uint32_t k) {
 static uint32_t full_snapshot(ctx *c) {
     struct psim_handle *h = c->h;
     if (c->snap != PSIM_NONE && !c->dirty) return c->snap;
+    if (h->oom) return 0;
     if (h->pay_out_n == h->pay_out_cap) {
-        h->pay_out_cap = h->pay_out_cap ? h->pay_out_cap * 2 : 64;
-        h->pay_out = (uint32_t *)realloc(h->pay_out, h->pay_out_cap * 2 * h->W * sizeof(uint32_t));
+        size_t cap = h->pay_out_cap ? h->pay_out_cap * 2 : 64;
+        uint32_t *p = (uint32_t *)realloc(h->pay_out, cap * 2 * h->W * sizeof(uint32_t));
+        if (!p) { h->oom = 1; return 0; }             /* the step fails: no later round reads the slot */
+        h->pay_out = p; h->pay_out_cap = cap;
     }
     memcpy(h->pay_out + h->pay_out_n * 2 * h->W, fb_row(h, c->me), 2 * h->W * sizeof(uint32_t));
     c->snap = (uint32_t)h->pay_out_n++;
@@ -1992,9 +2002,11 @@ int orc_broadcast(struct psim_handle *h, uint32_t root, uint32_t msg_id) {
 
 int orc_step(struct psim_handle *h, uint32_t n_rounds, psim_round_stats *stats) {
     psim_round_stats tmp;
+    if (h->oom) return PSIM_ESTATE;
     for (uint32_t i = 0; i < n_rounds; i++) {
         psim_round_stats *st = stats ? &stats[i] : &tmp;
         run_round(h, st);
+        if (h->oom) return PSIM_ENOMEM;            /* a round buffer could not grow: the handle is unusable */
         if (h->cfg.strict && st->overflow) return PSIM_ECAPACITY;   /* cfg.strict: fail loudly */
     }
     return PSIM_OK;
@@ -2240,8 +2252,9 @@ static void pack(const omsg *m, uint32_t *o) {
 }
 
 int orc_round_emit(struct psim_handle *h, psim_round_stats *st) {
+    if (h->oom) return PSIM_ESTATE;
     round_begin(h, st);
-    return PSIM_OK;
+    return h->oom ? PSIM_ENOMEM : PSIM_OK;
 }
 
 int orc_get_outbox(struct psim_handle *h, uint32_t *out, size_t cap, size_t *n) {
@@ -2253,6 +2266,7 @@ int orc_get_outbox(struct psim_handle *h, uint32_t *out, size_t cap, size_t *n) 
 
 int orc_round_absorb(struct psim_handle *h, const uint32_t *recs, size_t n) {
     msgvec in = {0, 0, 0};
+    if (h->oom) return PSIM_ESTATE;
     for (size_t i = 0; i < n; i++) {
         const uint32_t *o = recs + i * 16;
         omsg m;
@@ -2262,7 +2276,7 @@ int orc_round_absorb(struct psim_handle *h, const uint32_t *recs, size_t n) {
         m.a0 = o[4]; m.a1 = o[5]; m.a2 = o[6]; m.a3 = o[7];
         for (int k = 0; k < 8; k++) m.ex[k] = o[8 + k];
         if (m.dst < h->lo || m.dst >= h->hi) { free(in.v); return PSIM_ERANGE; }
-        vec_push(&in, &m);
+        if (!vec_push(&in, &m)) { free(in.v); h->oom = 1; return PSIM_ENOMEM; }
     }
     round_end(h, &in);
     free(in.v);

@@ -14,7 +14,8 @@ from .workloads import NONE
 
 
 class SimError(RuntimeError):
-    pass
+    """`rc`: the PSIM_* code of the failed call (None: not from the ABI)"""
+    rc = None
 
 
 def default_config(**kw):
@@ -59,7 +60,9 @@ class _Driver:
             msg = _abi.ERRORS.get(rc, str(rc))
             if self._errname is not None:
                 msg = self._errname(rc).decode()
-            raise SimError(f"{what}: {msg}")
+            err = SimError(f"{what}: {msg}")
+            err.rc = rc
+            raise err
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -22,7 +22,7 @@ import numpy as np
 
 from _oracle import Oracle
 from partisan_amd import _abi
-from partisan_amd.sim import _Driver
+from partisan_amd.sim import SimError, _Driver
 
 
 def _swap23(recs):
@@ -105,8 +105,18 @@ class Hybrid:
 
     # ---- events: every party makes the same call
     def _all(self, name, *a):
+        """a call one party refuses every party refuses, with the same code:
+        raised once every party has been asked"""
+        errs = []
         for p in self.parties:
-            getattr(p, name)(*a)
+            try:
+                getattr(p, name)(*a)
+            except SimError as e:
+                errs.append(e)
+        if errs:
+            assert len(errs) == len(self.parties) and len({e.rc for e in errs}) == 1, \
+                f"{name}: the parties disagree: {[str(e) for e in errs]}"
+            raise errs[0]
 
     def join(self, nodes, contacts): self._all("join", nodes, contacts)
     def crash(self, nodes): self._all("crash", nodes)

@@ -55,7 +55,7 @@ def doubling(make, n, seed, rounds, bcast_period=None, bcast_first=None, **cfg):
     return sim, st
 
 
-def multistep(make, n=4096, seed=9):
+def multistep(make, n=4096, seed=9, **cfg):
     """Rounds run several at a time between events (psim_step(k), k > 1),
     so the rank path runs batches of rounds (run_batch_ranked) whose
     fixed-size exchange was sized by quieter rounds: a broadcast after a
@@ -64,7 +64,7 @@ def multistep(make, n=4096, seed=9):
     exactly.  Doubling bootstrap, then 40 quiet rounds, a broadcast and 30
     rounds, 5 % crashes and 20 rounds, a half/half partition for 12 rounds,
     a broadcast and 25 rounds."""
-    sim = make(default_config(n_nodes=n, seed=seed))
+    sim = make(default_config(n_nodes=n, seed=seed, **cfg))
     st = [sim.run_schedule(W.doubling_join(n, seed), 20)]
     st.append(sim.step(40))
     sim.broadcast(0, 1)
@@ -101,6 +101,89 @@ def churn_partition(make, n=2048, seed=5, rounds=140, **cfg):
         bc(r)
     st = sim.run_schedule(W.doubling_join(n, seed), rounds, extra=hook)
     return sim, st
+
+
+def event_edges(make, n=1021, seed=5, rounds=100, bcast=True, **cfg):
+    """Event calls at their edges, several before one step: a partition
+    replaced without a clear and one set and cleared before the same step,
+    groups 0..2 and 254; crash and revive of the same ids in both orders; a
+    crash of nodes already down; a broadcast from a root that is down, and
+    from one that crashes in the same round; joins whose contact is down, or
+    the joiner itself; a join and a revive of live nodes (restarts); a second
+    broadcast from one root and one whose id shares a message slot (both
+    rejected, PSIM_EINVAL: the run goes on); a crash of every node but 0
+    (nodes_up 1 at round 56) and their rejoin by the doubling ramp over
+    rounds 57-66; node 0 broadcasts at rounds 20, 25, 35, 43, 70, 80 and 90.
+    bcast=False leaves the broadcasts out (pluggable handles).
+    Returns (sim, stats, outcomes): the code of every event call, in order."""
+    from partisan_amd.sim import SimError
+
+    assert n > 300
+    sim = make(default_config(n_nodes=n, seed=seed, **cfg))
+    ids = np.arange(n, dtype=np.uint32)
+    outcomes = []
+
+    def call(fn, *a):
+        try:
+            fn(*a)
+            outcomes.append((fn.__name__, 0))
+        except SimError as e:
+            outcomes.append((fn.__name__, e.rc))
+
+    def span(lo, hi):
+        return np.arange(lo, hi, dtype=np.uint32)
+
+    def bc(root, msg_id):
+        if bcast:
+            call(sim.broadcast, root, msg_id)
+    rejoin = {57 + r - 1: (v, c) for r, v, c in W.doubling_join(n, seed + 1)[1:]}
+    assert max(rejoin) < 70 <= rounds
+
+    def hook(r):
+        if r == 30:
+            call(sim.set_partition, (ids % 3).astype(np.uint8))
+        if r == 34:
+            call(sim.set_partition, np.where(ids % 5 == 0, 254, 0).astype(np.uint8))
+        if r == 38:
+            call(sim.set_partition, (ids % 2).astype(np.uint8))
+            call(sim.clear_partition)
+        if r == 40:
+            call(sim.crash, span(10, 40))
+            call(sim.revive, span(10, 40))
+        if r == 42:
+            call(sim.revive, span(50, 60))
+            call(sim.crash, span(50, 60))
+        if r == 44:
+            call(sim.crash, span(50, 70))
+        if r == 45:
+            bc(55, 1)
+        if r == 46:
+            call(sim.join, span(50, 60), np.full(10, 65, np.uint32))
+        if r == 47:
+            call(sim.join, span(60, 64), span(60, 64))
+        if r == 48:
+            call(sim.join, span(100, 110), span(110, 120))
+        if r == 49:
+            call(sim.revive, span(200, 210))
+        if r == 50:
+            call(sim.crash, span(300, 301))
+            bc(300, 2)
+        if r == 52:
+            bc(1, 3)
+            bc(1, 4)
+        if r == 53:
+            bc(2, 7)
+            bc(3, 71)
+        if r == 55:
+            call(sim.crash, span(1, n))
+        if r in rejoin:
+            call(sim.join, *rejoin[r])
+        # (node 0's broadcasts: the second of a stretch on makes lazy links, so
+        # the events meet IHAVEs in flight and outstanding entries)
+        if r in (20, 25, 35, 43, 70, 80, 90):
+            bc(0, 200 + r)
+    st = sim.run_schedule(W.doubling_join(n, seed), rounds, extra=hook)
+    return sim, st, outcomes
 
 
 def xbot_churn(make, n=2048, seed=5, rounds=140, period=10):
@@ -400,6 +483,29 @@ def pl_doubling(make, n, seed, rounds, strategy, fanout=0, crash_at=None, part_a
             sim.set_partition(W.half_partition(n))
         if part_at is not None and r == part_at + 10:
             sim.clear_partition()
+    st = sim.run_schedule(W.doubling_join(n, seed), rounds, extra=hook)
+    return sim, st
+
+
+def pl_restart_contact(make, n, seed, rounds, strategy, at=30, k=64, x=7, **cfg):
+    """SCAMP's join with a view of several members (scamp_v1:52-99,
+    scamp_v2:64-113: forward_subscription(Contact) to scamp_c random ones of
+    the members known before).  Every psim_join restarts the joiner with
+    init/1's view, itself alone, so the sublist has one candidate -- unless
+    subscriptions reach the joiner between its restart and its contact's
+    state: a doubling bootstrap; at `at` k live nodes rejoin through node x;
+    two rounds later x itself rejoins through node 0, and in the next round
+    the k forward_subscriptions meet x's fresh view, which keeps many of
+    them; x's own join then draws from that view."""
+    sim = make(default_config(n_nodes=n, seed=seed, manager=1, strategy=strategy, **cfg))
+    ids = np.arange(100, 100 + k, dtype=np.uint32)
+    assert 100 + k <= n and x < 100
+
+    def hook(r):
+        if r == at:
+            sim.join(ids, np.full(k, x, np.uint32))
+        if r == at + 2:
+            sim.join(np.array([x], np.uint32), np.zeros(1, np.uint32))
     st = sim.run_schedule(W.doubling_join(n, seed), rounds, extra=hook)
     return sim, st
 
