@@ -102,6 +102,7 @@ class Hybrid:
         self.resume_at, self.probes, self.on_outbound = resume_at, probes or {}, on_outbound
         self.n_out = self.n_in = 0
         self.resumed = False
+        self.tables = []
 
     # ---- events: every party makes the same call
     def _all(self, name, *a):
@@ -125,6 +126,50 @@ class Hybrid:
     def set_partition(self, group): self._all("set_partition", group)
     def clear_partition(self): self._all("clear_partition")
     def broadcast(self, root, msg_id): self._all("broadcast", root, msg_id)
+    def begin_omission(self, nodes): self._all("begin_omission", nodes)
+    def end_omission(self, nodes): self._all("end_omission", nodes)
+    def begin_send_omission(self, src, dst): self._all("begin_send_omission", src, dst)
+    def end_send_omission(self, src, dst): self._all("end_send_omission", src, dst)
+    def begin_receive_omission(self, src, dst): self._all("begin_receive_omission", src, dst)
+    def end_receive_omission(self, src, dst): self._all("end_receive_omission", src, dst)
+    def resolve_all_faults(self): self._all("resolve_all_faults")
+
+    # (the view-order tables are kept: a handle that takes over the engine's
+    # state needs them before its restore)
+    def set_bucket_table(self, buckets):
+        self._all("set_bucket_table", buckets)
+        self.tables.append(("set_bucket_table", buckets))
+
+    def set_phash_table(self, phash):
+        self._all("set_phash_table", phash)
+        self.tables.append(("set_phash_table", phash))
+
+    # ---- inspection: each party answers for the ids it owns
+    def _owned(self, name, first, count):
+        count = self.n - first if count is None else count
+        parts = []
+        for p in self.parties:
+            lo, hi = max(first, p.lo), min(first + count, p.hi)
+            if lo < hi:
+                parts.append(getattr(p, name)(lo, hi - lo))
+        return parts
+
+    def nodes(self, first=0, count=None):
+        return np.concatenate(self._owned("nodes", first, count))
+
+    def strategy_nodes(self, first=0, count=None):
+        return np.concatenate(self._owned("strategy_nodes", first, count))
+
+    def delivery(self, first=0, count=None):
+        p = self._owned("delivery", first, count)
+        return tuple(np.concatenate([x[i] for x in p]) for i in range(3))
+
+    def msg_slots(self):
+        """host state, the same at every party"""
+        out = [p.msg_slots() for p in self.parties]
+        for o in out[1:]:
+            assert all(np.array_equal(x, y) for x, y in zip(o, out[0])), "the parties disagree on the message slots"
+        return out[0]
 
     @property
     def round(self):

@@ -29,7 +29,20 @@ class LoopbackRanks:
             self.ranks.append(Simulator(c, comm=cid))
 
     def _all(self, name, *a):
-        out = [getattr(s, name)(*a) for s in self.ranks]
+        """a call one rank refuses every rank refuses, with the same code:
+        raised once every rank has been asked"""
+        from partisan_amd.sim import SimError
+
+        out, errs = [], []
+        for s in self.ranks:
+            try:
+                out.append(getattr(s, name)(*a))
+            except SimError as e:
+                errs.append(e)
+        if errs:
+            assert len(errs) == self.world and len({e.rc for e in errs}) == 1, \
+                f"{name}: the ranks disagree: {[str(e) for e in errs]}"
+            raise errs[0]
         return out[0]
 
     def _threads(self, name, *a):
@@ -61,6 +74,20 @@ class LoopbackRanks:
     def broadcast(self, root, msg_id): self._all("broadcast", root, msg_id)
     def set_bucket_table(self, buckets): self._all("set_bucket_table", buckets)
     def set_phash_table(self, phash): self._all("set_phash_table", phash)
+    def begin_omission(self, nodes): self._all("begin_omission", nodes)
+    def end_omission(self, nodes): self._all("end_omission", nodes)
+    def begin_send_omission(self, src, dst): self._all("begin_send_omission", src, dst)
+    def end_send_omission(self, src, dst): self._all("end_send_omission", src, dst)
+    def begin_receive_omission(self, src, dst): self._all("begin_receive_omission", src, dst)
+    def end_receive_omission(self, src, dst): self._all("end_receive_omission", src, dst)
+    def resolve_all_faults(self): self._all("resolve_all_faults")
+
+    def msg_slots(self):
+        """host state, the same on every rank"""
+        out = [s.msg_slots() for s in self.ranks]
+        for o in out[1:]:
+            assert all(np.array_equal(x, y) for x, y in zip(o, out[0])), "ranks disagree on the message slots"
+        return out[0]
 
     # ---- collectives: one thread per rank; every rank's stats are the
     # all-reduced ones
