@@ -2237,7 +2237,10 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
     const uint32_t l = lane_id();
     const uint32_t na = *kargs().n_alist;
     const uint64_t two58 = 1ull << 58;
-    unsigned long long v[R_N] = {};
+    // (a lane's counts in 32 bits -- its nodes' records are far fewer -- and
+    // widened for the sums; the digest is a 64-bit sum)
+    uint32_t v[R_N] = {};
+    unsigned long long vdg = 0;
     for (uint32_t base = blockIdx.x * blockDim.x; base < na; base += gridDim.x * blockDim.x) {
         KArgs& a = kargs();                           // (re-read per step, not held in SGPRs)
         const uint32_t P = base + threadIdx.x;
@@ -2249,6 +2252,8 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
         uint4 act0 = make_uint4(0, 0, 0, 0), act1 = act0;
         uint32_t me_part = 0;
         uint32_t hvm = 0;                             // the HyParView records among the first 32
+        uint32_t first = 0;                           // a lite node's leading relays: its inbox records below
+                                                      // `first` (relay_lead; 0: none, the lite kernel runs all)
         uint8_t fl0 = 0;                              // (the flag byte, read with the rows: read after
                                                       // the relays' stores, its wait drained them --
                                                       // gfx9 counts loads and stores in one in-order counter)
@@ -2271,6 +2276,7 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
             uint32_t hvn = 0;
             hvm = 0;
             bool all_relay = true, all_shuf = true, term_out = false, fjn = false;
+            uint32_t nf = ~0u;                        // the first HyParView record that is no SHUFFLE relay
             bcast = false; term = false; extra = (tf & DESC_SHUFFLE) != 0;
             const uint32_t av[8] = {act0.x, act0.y, act0.z, act0.w, act1.x, act1.y, act1.z, act1.w};
             // (four records' first 16 B issued before any is waited on: a
@@ -2308,6 +2314,7 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
                         // the active view -- the connection table's path, k_consume
                         term |= type == PSIM_MSG_SHUFFLE && !relays;
                         extra |= type == PSIM_MSG_SHUFFLE && relays;
+                        nf = type == PSIM_MSG_SHUFFLE && relays ? nf : min(nf, j + q);
                         if (type == PSIM_MSG_SHUFFLE && !relays) {
                             bool in = false;
 #pragma unroll
@@ -2367,6 +2374,13 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
             // SHUFFLE terminals and replies (with whatever relays and shuffle
             // start come with them): k_consume_lite
             lite = !heavy && hvn && !(all_relay && h.act_n > 1);
+            // its SHUFFLE relays ahead of the first terminal or reply run on
+            // this lane, below: a relay changes nothing of the node but its
+            // draw counter and outbox count, and handlers run in inbox order,
+            // so these relays' draws and sequence numbers are known here (a
+            // later one's follow a merge's evictions: the lite kernel's).  An
+            // inbox past 32 records (hvm holds 32) stays whole.
+            first = a.relay_lead && lite && ik <= 32 && nf < ik ? nf : 0u;
             // a due shuffle with nothing else heavy: k_shuf, after the relays
             shuf = !heavy && !lite && (tf & DESC_SHUFFLE);
             maps = maps || exits || (tf & DESC_PROMO) || h.conn_cl;   // move_to_active: current_id
@@ -2445,32 +2459,36 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
                     uint4* desc = k == 0 ? a.desc_slow : k == 1 ? a.desc_pt : k == 2 || k == 5 || k >= 9 ? a.desc_ptl
                                 : k == 3 ? a.desc_shuf : a.desc_lite;
                     const uint32_t nl = a.n_local;
+                    // (the lite list's inbox run starts at the first record
+                    // this lane leaves the lite kernel, whose prefetch of
+                    // senders, type words and exchanges then starts there)
                     desc[k == 5 || k == 6 ? nl - 1 - at : k == 7 || k == 9 ? nl + at
                          : k == 8 || k == 10 ? 2 * nl - 1 - at : at] =
-                        k == 0 && maps ? make_uint4(D.x, D.y, D.z | DESC_MAPS_BIT, D.w) : D;
+                        k == 0 && maps ? make_uint4(D.x, D.y, D.z | DESC_MAPS_BIT, D.w)
+                        : k == 4 || (k >= 6 && k <= 8) ? make_uint4(D.x, D.y + first, D.z - first, D.w) : D;
                 }
         }
-        if (P < na && lite && !heavy) {
-            // the lite node's connection bits (psim_lite.hip connect_ok)
-            uint32_t cm = 0;
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-                cm |= ((upm[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) == me_part ? 1u << j : 0u;
-            kargs().lite_cm[D.x - kargs().lo] = (uint8_t)cm;
-        }
-        if (P >= na || heavy || lite) continue;
+        if (P >= na || heavy) continue;
         const uint32_t id = D.x;
         const size_t li = id - a.lo;
         const uint32_t A[8] = {act0.x, act0.y, act0.z, act0.w, act1.x, act1.y, act1.z, act1.w};
         uint64_t rng = h.rng;
         uint32_t seq = 0;
+        // bit j: active member j is up in this node's partition group -- the
+        // relays' send test, and a lite node's connection bits (psim_lite.h
+        // connect_ok)
+        uint32_t cm = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            cm |= ((upm[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) == me_part ? 1u << j : 0u;
         // the SHUFFLE / FORWARD_JOIN relays, in inbox order: a relay lane's
-        // HyParView records (hvm; every record of an inbox past 32); a
-        // Plumtree record's type word is not read again -- each such load
-        // after a relay's stores waited for them (one in-order counter)
+        // HyParView records (hvm; every record of an inbox past 32), a lite
+        // lane's below `first`; a Plumtree record's type word is not read
+        // again -- each such load after a relay's stores waited for them (one
+        // in-order counter)
         const bool big = ik > 32;
-        uint32_t rm = relay ? hvm : 0u;
-        for (uint32_t jr = 0; relay && (big ? jr < ik : rm != 0); jr++) {
+        uint32_t rm = relay ? hvm : hvm & ((1u << first) - 1u);     // (first < 32, 0 off the lite list)
+        for (uint32_t jr = 0; big ? relay && jr < ik : rm != 0; jr++) {
             if (!big) {
                 jr = (uint32_t)__ffs(rm) - 1;
                 rm &= rm - 1;
@@ -2482,7 +2500,8 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
             const uint32_t ttl = (tt >> 8) & 0xFF, nex = (tt >> 16) & 0xFF, src = rp->src;
             // (FORWARD_JOIN: the joiner and its epoch)
             const uint32_t jq = fj ? rp->a0 : NONE, jpe = fj ? rp->a1 : 0u;
-            v[fj ? R_DELIV_FJ : R_DELIV]++;
+            v[R_DELIV] += fj ? 0u : 1u;
+            v[R_DELIV_FJ] += fj ? 1u : 0u;
             // select_random(Active, [Sender, Myself]) (hv:1346-1356); a
             // FORWARD_JOIN's omits the joiner too (hv:867-870)
             uint32_t elig = 0;
@@ -2502,12 +2521,8 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
                 for (uint32_t j = 0; j < k; j++) e &= e - 1;
                 const uint32_t jr_ = (uint32_t)__ffs(e) - 1;
                 const uint32_t r = A[jr_];
-                uint32_t up = 0;
-#pragma unroll
-                for (int j = 0; j < 8; j++)
-                    if ((uint32_t)j == jr_) up = (upm[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
                 // do_send_message: maybe_connect + find, then the dispatch draw
-                if (r < a.n_nodes && up == me_part) {
+                if (r < a.n_nodes && ((cm >> jr_) & 1u)) {
                     rng++;
                     uint32_t X[8] = {};
                     if (!fj) {
@@ -2517,18 +2532,28 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
 #pragma unroll
                         for (int j = 0; j < 8; j++) X[j] = (uint32_t)j < nex ? E[j] : 0u;
                     }
-                    v[R_DIGEST] += relay_emit(a, D.w + seq, r, id,
+                    vdg += relay_emit(a, D.w + seq, r, id,
                                               fj ? PSIM_MSG_FORWARD_JOIN | ((ttl - 1) << 8)
                                                  : PSIM_MSG_SHUFFLE | ((ttl - 1) << 8) | (nex << 16),
                                               seq, fj ? jq : 0u, jpe, 0u, X);
                     seq++;
-                    v[fj ? R_FJ : R_SHUF]++;
+                    v[R_SHUF] += fj ? 0u : 1u;
+                    v[R_FJ] += fj ? 1u : 0u;
                 } else {
                     v[R_FAIL]++;
                 }
             }
         }
         if (rng != h.rng) a.hdr[li].rng = rng;
+        if (lite) {
+            // the lite node's connection bits and the records emitted here
+            // -- fewer than the relays run when a send failed: the node's
+            // first sequence number and outbox slot.  The lite kernel counts
+            // the node, checks the bound on its total and writes the outbox
+            // count and the rest of the header.
+            a.lite_cm[li] = (uint16_t)(cm | (seq << 8));
+            continue;
+        }
         a.ocnt[li] = seq;
         v[R_BOUND] += seq > oend - D.w ? 1u : 0u;
         if (!to_pt) {                                 // (k_ptl / k_pt write the byte of their nodes)
@@ -2539,11 +2564,18 @@ __global__ void __launch_bounds__(256, PSIM_RELAY_WAVES) k_relay(RoundArgs) {
     }
     // wave sums, then one LDS atomic per wave and counter
 #pragma unroll
-    for (int k = 0; k < R_N; k++)
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-    if (l == 0)
-        for (int k = 0; k < R_N; k++)
-            if (v[k]) atomicAdd(&sst[k], v[k]);
+    for (int k = 0; k < R_N; k++) {
+        // (the lane from threadIdx.x, which the loop keeps anyway: `l` held
+        // across the loop for __shfl_xor was the kernel's one spill)
+        unsigned long long t = k == R_DIGEST ? vdg : (unsigned long long)v[k];
+        for (uint32_t o = 32; o > 0; o >>= 1) {
+            const int from = (int)(((threadIdx.x & 63u) ^ o) << 2);
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)(uint32_t)t);
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)(uint32_t)(t >> 32));
+            t += ((unsigned long long)hi << 32) | lo;
+        }
+        if ((threadIdx.x & 63u) == 0 && t) atomicAdd(&sst[k], t);
+    }
     __syncthreads();
     uint64_t* row = kargs().stat_relay + (size_t)blockIdx.x * NST;
     for (uint32_t k = threadIdx.x; k < NST; k += blockDim.x)

@@ -2383,7 +2383,7 @@ struct Shard {
     // replicated (global id)
     DBuf<uint8_t> flags, part;
     DBuf<upart_t> upart;                // k_node_prep's up-and-partition pairs (RoundArgs::upart)
-    DBuf<uint8_t> lite_cm;              // k_relay's connection bits of lite-list nodes (RoundArgs::lite_cm)
+    DBuf<uint16_t> lite_cm;             // k_relay's connection bits and emitted counts of lite-list nodes (RoundArgs::lite_cm)
     DBuf<uint32_t> crash_bits;   // RoundArgs::crash_bits
     DBuf<uint8_t> btab;          // RoundArgs::btab (psim_set_bucket_table), global id
     // local rows
@@ -2597,6 +2597,21 @@ int ptl_early_knob() {
     return v;
 }
 
+// PSIM_RELAY_LEAD, read once: 1 = k_relay's lane of a lite node runs the
+// SHUFFLE relays ahead of the node's first terminal or reply and hands the
+// lite kernel the rest of the inbox (RoundArgs::relay_lead, lite_cm); 0 = the
+// lite kernel runs every record of its nodes.  The wave-per-node kernel
+// (PSIM_LITE_WAVE=1, A/B) always runs them all: its writeback rewrites the
+// slot before a node's first own record when it emitted none (flush_recs).
+constexpr int RELAY_LEAD_DEFAULT = 1;
+bool relay_lead_knob() {
+    static const bool v = [] {
+        const char* e = getenv("PSIM_RELAY_LEAD");
+        return e && *e ? atoi(e) != 0 : RELAY_LEAD_DEFAULT != 0;
+    }();
+    return v;
+}
+
 // PSIM_PREP_FUSED, read once: 1 = inside a batch the route of a round without
 // a round-end half prepares the next round (k_bucket_route, RoutePrep) and
 // that round launches no k_node_prep; 0 = every round launches k_node_prep.
@@ -2666,6 +2681,7 @@ RoundArgs make_args(psim_handle* h, Shard* s) {
     a.pl = c.manager == PSIM_MANAGER_PLUGGABLE;
     a.xbot = c.manager == PSIM_MANAGER_XBOT; a.xbot_period = c.xbot_period;
     a.ptl_split = ptl_early_knob() != 0;
+    a.relay_lead = relay_lead_knob() && h->lite.kernel != psim::k_consume_lite;
     a.strategy = c.strategy; a.periodic = c.periodic_interval; a.scamp_c = c.scamp_c;
     a.fanout = c.fanout; a.fw = h->fw; a.tomb = h->tomb;
     a.fbits = s->fbits.p; a.sview = s->sview.p; a.sinv = s->sinv.p;

@@ -29,6 +29,7 @@ struct RoundArgs {
     uint32_t shuffle_period, promotion_period, random_promotion, plumtree, lazy_tick_period;
     uint32_t xbot, xbot_period;   // X-BOT manager (PSIM_MANAGER_XBOT) and its xbot_execution period
     uint32_t ptl_split;           // k_relay files k_ptl's nodes by dependency (n_ptl; PSIM_PTL_EARLY != 0)
+    uint32_t relay_lead;          // k_relay's lanes run a lite node's leading SHUFFLE relays (PSIM_RELAY_LEAD != 0)
     // per-round scalars
     uint32_t crash_round, tracked_msg;
     uint32_t upart_dirty;       // this round's events changed F_UP or a partition: k_node_prep rebuilds upart
@@ -48,9 +49,12 @@ struct RoundArgs {
     upart_t* upart;
     // per local node of k_relay's lite list: bit j = active member j is up in
     // this node's partition group (k_relay reads the pairs for it before its
-    // list appends; the lite kernel reads the byte with the node's rows, a node
-    // ahead, instead of eight dependent pair loads as the node starts)
-    uint8_t* lite_cm;
+    // list appends; the lite kernel reads the word with the node's rows, a node
+    // ahead, instead of eight dependent pair loads as the node starts) in the
+    // low byte; in the high byte the records k_relay's lane emitted for the
+    // node's leading SHUFFLE relays (relay_lead; 0 without): the lite node's
+    // first sequence number and outbox slot
+    uint16_t* lite_cm;
     // this round's crashed ids, one bit per CRASH_GRAIN ids (replicated,
     // zero outside crash rounds): a filter in L2 in front of the flag bytes
     const uint32_t* crash_bits;
@@ -290,6 +294,7 @@ constexpr uint32_t layout_sig() {
     uint32_t h = 0x811C9DC5u;
     const uint64_t v[] = {
         PSIM_ABI_VERSION, sizeof(RoundArgs), offsetof(RoundArgs, flags), offsetof(RoundArgs, upart),
+        offsetof(RoundArgs, relay_lead), sizeof(*RoundArgs().lite_cm),
         offsetof(RoundArgs, hdr), offsetof(RoundArgs, conn), offsetof(RoundArgs, outx_rows),
         offsetof(RoundArgs, desc), offsetof(RoundArgs, desc_lite), offsetof(RoundArgs, stat_ptle), offsetof(RoundArgs, stat_pt),
         offsetof(RoundArgs, rec_out), offsetof(RoundArgs, okey), offsetof(RoundArgs, ktime),

@@ -687,7 +687,7 @@ struct In {
     uint4 D;
     uint32_t r0, r1, w9, A, part;
     typename Pas<W>::Row P;          // this lane's share of the passive row
-    uint32_t cm, oe;                 // k_relay's connection bits; obase[row + 1] (low word)
+    uint32_t cm, oe;                 // k_relay's connection bits | its emitted count << 8; obase[row + 1] (low word)
     uint32_t SRC, TT;                // lane l: sender and type word of inbox record l
     uint32_t EXP;                    // lane l: exchange id l & 7 of inbox record l >> 3
 };
@@ -742,7 +742,9 @@ DEV void begin(Node<W>& x, const In<W>& in) {
     x.act_n = in.w9 & 0xFF; x.pas_n = (in.w9 >> 8) & 0xFF;
     x.A = l < x.act_n ? in.A : 0u;
     x.pas.set(in.P, x.pas_n);
-    x.seq = 0; x.flushed = 0;
+    // after the records k_relay's lane emitted for the node's leading SHUFFLE
+    // relays (RoundArgs::lite_cm's high byte; the inbox run starts past them)
+    x.seq = in.cm >> 8; x.flushed = x.seq;
     x.dcb = ~0ull;
 }
 
@@ -909,7 +911,7 @@ DEV void lite_kernel(const uint32_t bid, const uint32_t nblk, uint32_t* const po
             LSTAMP(w, 8);
             begin(x, in);
             // the connection bits and the outbox bound, loaded with the rows
-            x.AF = in.cm | (min(in.oe - x.ob, 0xFFFFFFu) << 8);
+            x.AF = (in.cm & 0xFFu) | (min(in.oe - x.ob, 0xFFFFFFu) << 8);
             // the next node's inputs, in flight while this one runs
             const uint32_t nx = i + step, nnx = i + 2 * step;
             In<W> inn = load_in<W>(kargs(), Dn);
