@@ -444,6 +444,41 @@ static ERL_NIF_TERM nif_strategy_histograms(ErlNifEnv *env, int argc, const ERL_
     return enif_make_tuple2(env, enif_make_atom(env, "ok"), m);
 }
 
+/* graph_metrics_nif(Ref, SourcesBin, MaxLevels) -> {ok, #{...}} : path lengths
+ * from the sources (little-endian u32 ids, at most PSIM_GRAPH_SOURCES) and
+ * the clustering of the overlay (psim_graph_metrics) */
+static ERL_NIF_TERM nif_graph_metrics(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+    sim_res *r; ErlNifBinary b; unsigned max_levels;
+    psim_graph_metrics gm;
+    uint32_t src[PSIM_GRAPH_SOURCES];
+    if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r) || !enif_inspect_binary(env, argv[1], &b) ||
+        !enif_get_uint(env, argv[2], &max_levels) || b.size % 4 || b.size > sizeof src)
+        return enif_make_badarg(env);
+    memcpy(src, b.data, b.size);      /* (binary data need not be 4-byte aligned) */
+    enif_mutex_lock(r->mu);
+    int rc = psim_get_graph_metrics(r->h, src, b.size / 4, max_levels, &gm);
+    enif_mutex_unlock(r->mu);
+    if (rc) return err(env, rc);
+    ERL_NIF_TERM m = enif_make_new_map(env);
+    ERL_NIF_TERM v[PSIM_HIST_BINS > PSIM_GRAPH_SOURCES ? PSIM_HIST_BINS : PSIM_GRAPH_SOURCES];
+    for (int k = 0; k < PSIM_HIST_BINS; k++) v[k] = enif_make_uint64(env, gm.dist[k]);
+    enif_make_map_put(env, m, enif_make_atom(env, "dist"), enif_make_list_from_array(env, v, PSIM_HIST_BINS), &m);
+    for (int k = 0; k < PSIM_GRAPH_SOURCES; k++) v[k] = enif_make_uint64(env, gm.reach[k]);
+    enif_make_map_put(env, m, enif_make_atom(env, "reach"), enif_make_list_from_array(env, v, PSIM_GRAPH_SOURCES),
+                      &m);
+    for (int k = 0; k < PSIM_GRAPH_SOURCES; k++) v[k] = enif_make_uint(env, gm.ecc[k]);
+    enif_make_map_put(env, m, enif_make_atom(env, "ecc"), enif_make_list_from_array(env, v, PSIM_GRAPH_SOURCES), &m);
+    const char *snames[14] = {"n_up", "links", "cl_nodes", "cl_closed", "cl_pairs", "cl_sum_q32", "sources_live",
+                              "dist_sum", "pairs_reached", "pairs_unreached", "ecc_max", "levels", "truncated",
+                              NULL};
+    const uint64_t svals[14] = {gm.n_up, gm.links, gm.cl_nodes, gm.cl_closed, gm.cl_pairs, gm.cl_sum_q32,
+                                gm.sources_live, gm.dist_sum, gm.pairs_reached, gm.pairs_unreached, gm.ecc_max,
+                                gm.levels, gm.truncated, 0};
+    for (int k = 0; snames[k]; k++)
+        enif_make_map_put(env, m, enif_make_atom(env, snames[k]), enif_make_uint64(env, svals[k]), &m);
+    return enif_make_tuple2(env, enif_make_atom(env, "ok"), m);
+}
+
 /* snapshot(Ref) -> {ok, Binary} ; restore(Ref, Binary) -> ok */
 static ERL_NIF_TERM nif_snapshot(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
     sim_res *r;
@@ -582,6 +617,7 @@ static ErlNifFunc funcs[] = {
     {"delivery_nif", 2, nif_delivery, 0},
     {"histograms", 1, nif_histograms, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"strategy_histograms", 1, nif_strategy_histograms, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"graph_metrics_nif", 3, nif_graph_metrics, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"set_partition_nif", 2, nif_set_partition, 0},
     {"clear_partition_nif", 1, nif_clear_partition, 0},
     {"set_bucket_table_nif", 2, nif_set_bucket_table, 0},

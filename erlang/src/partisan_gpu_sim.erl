@@ -8,7 +8,7 @@
 %% bounded back-off, so callers may match on success directly.
 -module(partisan_gpu_sim).
 -export([create/1, join/3, crash/2, revive/2, leave/2, leave_node/3, broadcast/3, step/2, active/2, members/3,
-         delivery/2, histograms/1, strategy_histograms/1, snapshot/1, restore/2, set_partition/2, clear_partition/1, node/2,
+         delivery/2, histograms/1, strategy_histograms/1, graph_metrics/3, snapshot/1, restore/2, set_partition/2, clear_partition/1, node/2,
          begin_send_omission/3, end_send_omission/3, begin_receive_omission/3, end_receive_omission/3,
          begin_omission/2, end_omission/2, clear_faults/1, msg_slots/1, set_bucket_table/2, phash_buckets/2,
          set_phash_table/2, phash_table/2, spec_ip/1, round_emit/1, outbound/1, round_absorb/2]).
@@ -60,6 +60,13 @@ histograms(_Sim) -> erlang:nif_error(nif_not_loaded).
 %% overlay statistics of a pluggable manager handle (psim_strategy_histograms)
 %% as a map (dirty NIF); {error, unsupported} on HyParView and X-BOT handles
 strategy_histograms(_Sim) -> erlang:nif_error(nif_not_loaded).
+%% path lengths from Sources (a list of at most 64 distinct ids; [] leaves the
+%% path half zero) and the clustering of the overlay (psim_graph_metrics) as a
+%% map; MaxLevels 0: the engine's cap.  HyParView, X-BOT and SCAMP handles;
+%% {error, unsupported} on full-membership and host-exchange handles.  The
+%% NIF is dirty and waits for the handle's mutex itself.
+graph_metrics(Sim, Sources, MaxLevels) -> graph_metrics_nif(Sim, pack(Sources), MaxLevels).
+graph_metrics_nif(_Sim, _Sources, _MaxLevels) -> erlang:nif_error(nif_not_loaded).
 %% whole-simulation state as a binary, and back into a handle of the same config (dirty NIFs)
 snapshot(_Sim) -> erlang:nif_error(nif_not_loaded).
 restore(_Sim, _Bin) -> erlang:nif_error(nif_not_loaded).

@@ -354,6 +354,45 @@ typedef struct psim_strategy_histograms {
     uint64_t reserved[8];
 } psim_strategy_histograms;
 
+/* Path lengths and clustering of the overlay, computed on the device
+ * (DESIGN.md "Path lengths and clustering").  The link set L is the one the
+ * two structs above count: for HyParView and X-BOT handles the ordered pairs
+ * (i, p), i live, p in i's active view, p != i, p live
+ * (psim_histograms.active_links); for SCAMP v1 / v2 handles the distinct
+ * ordered pairs of psim_strategy_histograms.links.  N(i): the out-neighbours
+ * of i in L, k_i = |N(i)|.  Bins as above: bin k = value k, the last bin =
+ * PSIM_HIST_BINS - 1 or more.
+ *   Clustering, over every live node: closed_i = the ordered pairs (a, b),
+ *     a, b in N(i), a != b, with (a, b) in L.  cl_closed / cl_pairs is the
+ *     transitivity; the mean local coefficient is cl_sum_q32 / 2^32 divided
+ *     by n_up or by cl_nodes (fixed point: bit-exact whatever the order of
+ *     the sum).
+ *   Path lengths: directed shortest distances d(s, v) over L from the live
+ *     nodes among the caller's sources, slot j = sources[j]; a dead source's
+ *     slot stays zero. */
+#define PSIM_GRAPH_SOURCES 64
+#define PSIM_GRAPH_MAX_LEVELS 4096
+typedef struct psim_graph_metrics {
+    uint64_t n_up;                           /* live nodes */
+    uint64_t links;                          /* |L| */
+    uint64_t cl_nodes;                       /* live nodes with k_i >= 2 */
+    uint64_t cl_closed;                      /* sum of closed_i */
+    uint64_t cl_pairs;                       /* sum of k_i (k_i - 1) */
+    uint64_t cl_sum_q32;                     /* sum over k_i >= 2 of floor(closed_i 2^32 / (k_i (k_i - 1))) */
+    uint64_t sources_live;                   /* live nodes among the sources */
+    uint64_t dist[PSIM_HIST_BINS];           /* pairs (slot j, live v != sources[j]) by finite distance; bin 0: 0 */
+    uint64_t dist_sum;                       /* the exact sum of those distances (not saturated) */
+    uint64_t pairs_reached;                  /* their number */
+    uint64_t pairs_unreached;                /* sources_live (n_up - 1) - pairs_reached */
+    uint64_t reach[PSIM_GRAPH_SOURCES];      /* per slot: the nodes reached */
+    uint32_t ecc[PSIM_GRAPH_SOURCES];        /* per slot: the largest finite distance */
+    uint64_t ecc_max;
+    uint64_t levels;                         /* BFS levels run (the last one may have found nothing) */
+    uint64_t truncated;                      /* 1: the level cap ended the BFS with a frontier still open;
+                                                pairs farther apart than the cap count as unreached */
+    uint64_t reserved[8];
+} psim_graph_metrics;
+
 typedef struct psim_handle psim_handle;
 
 void psim_default_config(psim_config *cfg);
@@ -491,6 +530,21 @@ int psim_get_histograms(psim_handle *h, psim_histograms *out);
  * run without it.  Like psim_get_histograms a collective on rank handles
  * (every rank must call; every rank gets the same struct). */
 int psim_get_strategy_histograms(psim_handle *h, psim_strategy_histograms *out);
+/* Path lengths from up to PSIM_GRAPH_SOURCES sources (one bit-parallel BFS)
+ * and the clustering of the whole overlay (psim_graph_metrics above), on the
+ * device, for HyParView, X-BOT and SCAMP v1 / v2 handles.  n_sources == 0
+ * fills the clustering half only.  max_levels caps the BFS: 0 means
+ * PSIM_GRAPH_MAX_LEVELS, and larger values are clamped to it.
+ * PSIM_EINVAL for a null h or out, null sources with n_sources > 0,
+ * n_sources > PSIM_GRAPH_SOURCES or a repeated source; PSIM_ERANGE for a
+ * source >= n_nodes (a dead source is legal and skipped); PSIM_EUNSUPPORTED
+ * for full-membership handles (their overlay is the member set) and
+ * host-exchange handles; PSIM_ESTATE with a round open.  Read-only: the
+ * rounds stepped after it are those of a run without it.  A collective on
+ * rank handles (every rank calls with the same arguments; every rank gets the
+ * same struct). */
+int psim_get_graph_metrics(psim_handle *h, const uint32_t *sources, size_t n_sources, uint32_t max_levels,
+                           psim_graph_metrics *out);
 /* Snapshot of the whole simulation state of this process (node rows,
  * in-flight messages, round, events not yet applied are not included):
  * with buf == NULL (or cap too small) only *need is set.  psim_restore
@@ -618,9 +672,9 @@ int psim_loopback_comm_id(void *buf, size_t cap);
  * psim_revive, psim_crash, psim_leave, psim_set_partition, psim_broadcast,
  * the omission calls, the view-order tables), so an outside node's start,
  * death, partition group and broadcast slots are known here as a remote
- * rank's are.  psim_step, psim_leave_node, psim_get_histograms and
- * psim_get_strategy_histograms answer PSIM_EUNSUPPORTED (the last three
- * need a collective across the parties).
+ * rank's are.  psim_step, psim_leave_node, psim_get_histograms,
+ * psim_get_strategy_histograms and psim_get_graph_metrics answer
+ * PSIM_EUNSUPPORTED (the last four need a collective across the parties).
  *   A round is three calls:
  * psim_round_emit    applies the pending events and runs the owned nodes'
  *     round up to its owner partition.  PSIM_ESTATE with a round open,

@@ -136,6 +136,23 @@ class PsimStrategyHistograms(C.Structure):
     ]
 
 
+GRAPH_SOURCES, GRAPH_MAX_LEVELS = 64, 4096
+
+
+class PsimGraphMetrics(C.Structure):
+    _fields_ = [
+        ("n_up", C.c_uint64), ("links", C.c_uint64),
+        ("cl_nodes", C.c_uint64), ("cl_closed", C.c_uint64), ("cl_pairs", C.c_uint64),
+        ("cl_sum_q32", C.c_uint64),
+        ("sources_live", C.c_uint64),
+        ("dist", C.c_uint64 * HIST_BINS), ("dist_sum", C.c_uint64),
+        ("pairs_reached", C.c_uint64), ("pairs_unreached", C.c_uint64),
+        ("reach", C.c_uint64 * GRAPH_SOURCES), ("ecc", C.c_uint32 * GRAPH_SOURCES),
+        ("ecc_max", C.c_uint64), ("levels", C.c_uint64), ("truncated", C.c_uint64),
+        ("reserved", C.c_uint64 * 8),
+    ]
+
+
 NODE_VIEW_DTYPE = np.dtype(PsimNodeView)
 STRATEGY_VIEW_DTYPE = np.dtype(PsimStrategyView)
 STATS_DTYPE = np.dtype(PsimRoundStats)
@@ -185,6 +202,7 @@ GPU_ONLY = {
     "debug_kernel_counts": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int]),
     # (no oracle twin: the tests' reference is numpy over the oracle's views)
     "get_strategy_histograms": (C.c_int, [_H, C.POINTER(PsimStrategyHistograms)]),
+    "get_graph_metrics": (C.c_int, [_H, _P32, C.c_size_t, C.c_uint32, C.POINTER(PsimGraphMetrics)]),
 }
 # the host boundary (host-exchange handles: sim.HostSim, wire.check)
 HOST_BOUNDARY = {

@@ -2265,6 +2265,207 @@ __global__ void __launch_bounds__(BLK) k_sh_full(const uint32_t* __restrict__ fb
     }
 }
 
+// ------------------------------------- path lengths and clustering --
+// psim_get_graph_metrics.  Every kernel reads the link set L as rows: node
+// i's cnt[i] ids at adj + off[i] (the pluggable handles' CSR, as k_sh_rows
+// packs it: distinct, != i, live) or, off == nullptr, at
+// adj + i * PSIM_ACTIVE_CAP (HyParView's rows after k_gm_filter, the same
+// three properties).
+//   k_gm_cluster_hv / k_gm_cluster   closed_i = sum over a in N(i) of
+//                      |N(a) & N(i)| (no row holds its own node, so b != a)
+//   k_gm_init / k_gm_push / k_gm_level   the bit-parallel BFS: bit j of a
+//                      node's word = reached from source slot j
+enum { GM_NUP = 0, GM_LINKS, GM_NODES, GM_CLOSED, GM_PAIRS, GM_Q32, GM_N };
+constexpr uint32_t GM_TAB = 256;      // k_gm_cluster: hash slots a wave keeps for one N(i) (<= PSIM_SVIEW_CAP ids)
+
+__global__ void k_gm_filter(const uint8_t* __restrict__ gan, const uint32_t* __restrict__ gact,
+                            const uint8_t* __restrict__ flags, uint32_t n, uint32_t* fadj, uint8_t* fcnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t c = 0;
+    if (flags[i] & F_UP) {
+        const uint32_t* row = gact + (size_t)i * PSIM_ACTIVE_CAP;
+        const uint32_t len = min((uint32_t)gan[i], (uint32_t)PSIM_ACTIVE_CAP);
+        for (uint32_t k = 0; k < len; k++) {
+            const uint32_t p = row[k];
+            if (p == i || p >= n || !(flags[p] & F_UP)) continue;
+            bool dup = false;
+            for (uint32_t q = 0; q < k; q++) dup |= row[q] == p;
+            if (!dup) fadj[(size_t)i * PSIM_ACTIVE_CAP + c++] = p;
+        }
+    }
+    fcnt[i] = (uint8_t)c;
+}
+
+// a node's share of the clustering sums, into the block's LDS words
+DEV void gm_cluster_add(unsigned long long* sh, uint32_t k, uint32_t closed) {
+    atomicAdd(&sh[GM_NUP], 1ull);
+    if (k) atomicAdd(&sh[GM_LINKS], (unsigned long long)k);
+    if (k < 2) return;
+    const unsigned long long pairs = (unsigned long long)k * (k - 1);
+    atomicAdd(&sh[GM_NODES], 1ull);
+    atomicAdd(&sh[GM_PAIRS], pairs);
+    if (closed) {
+        atomicAdd(&sh[GM_CLOSED], (unsigned long long)closed);
+        atomicAdd(&sh[GM_Q32], ((unsigned long long)closed << 32) / pairs);
+    }
+}
+
+// HyParView rows: 8 lanes a node, lane g takes neighbour g's row
+__global__ void __launch_bounds__(BLK) k_gm_cluster_hv(const uint8_t* __restrict__ cnt,
+                                                       const uint32_t* __restrict__ adj,
+                                                       const uint8_t* __restrict__ flags, uint32_t n,
+                                                       unsigned long long* gm) {
+    static_assert(PSIM_ACTIVE_CAP == 8, "one 8-lane group per node");
+    __shared__ unsigned long long sh[GM_N];
+    if (threadIdx.x < GM_N) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) / PSIM_ACTIVE_CAP, g = threadIdx.x % PSIM_ACTIVE_CAP;
+    const bool up = i < n && (flags[i] & F_UP);
+    const uint32_t k = up ? cnt[i] : 0;
+    uint32_t mine[PSIM_ACTIVE_CAP];
+#pragma unroll
+    for (uint32_t r = 0; r < PSIM_ACTIVE_CAP; r++) mine[r] = r < k ? adj[(size_t)i * PSIM_ACTIVE_CAP + r] : PSIM_NONE;
+    uint32_t c = 0;
+    if (g < k && k >= 2) {
+        const uint32_t a = adj[(size_t)i * PSIM_ACTIVE_CAP + g];
+        const uint32_t* row = adj + (size_t)a * PSIM_ACTIVE_CAP;
+        for (uint32_t q = 0, ka = cnt[a]; q < ka; q++) {
+            const uint32_t b = row[q];
+#pragma unroll
+            for (uint32_t r = 0; r < PSIM_ACTIVE_CAP; r++) c += mine[r] == b ? 1u : 0u;
+        }
+    }
+    for (int d = PSIM_ACTIVE_CAP / 2; d; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
+    if (up && g == 0) gm_cluster_add(sh, k, c);
+    __syncthreads();
+    if (threadIdx.x < GM_N && sh[threadIdx.x]) atomicAdd(&gm[threadIdx.x], sh[threadIdx.x]);
+}
+
+DEV uint32_t gm_hash(uint32_t id) { return (id * 2654435761u) >> 24; }     // (GM_TAB = 2^8 slots)
+
+// CSR rows (up to PSIM_SVIEW_CAP ids): a wave a node.  N(i) sits in the
+// wave's LDS hash table (at most half full); each neighbour's row is read
+// coalesced, two ids a lane as sh_row_load holds a view, and probed against it
+__global__ void __launch_bounds__(BLK) k_gm_cluster(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
+                                                    const uint32_t* __restrict__ adj,
+                                                    const uint8_t* __restrict__ flags, uint32_t n,
+                                                    unsigned long long* gm) {
+    static_assert(GM_TAB == 256 && GM_TAB >= 2 * PSIM_SVIEW_CAP, "gm_hash gives 8 bits; the table stays half empty");
+    __shared__ uint32_t tab_all[BLK / 64][GM_TAB];
+    __shared__ unsigned long long sh[GM_N];
+    const uint32_t w = threadIdx.x >> 6, l = lane_id();
+    uint32_t* tab = tab_all[w];
+    for (uint32_t q = l; q < GM_TAB; q += 64) tab[q] = PSIM_NONE;
+    if (threadIdx.x < GM_N) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * (BLK / 64) + w;                          // (uniform per wave)
+    const bool up = i < n && (flags[i] & F_UP);
+    const uint32_t k = up ? min((uint32_t)cnt[i], (uint32_t)PSIM_SVIEW_CAP) : 0;
+    uint32_t a = PSIM_NONE, b = PSIM_NONE;
+    if (k >= 2) {
+        sh_row_load(adj + off[i], k, a, b);
+        for (int half = 0; half < 2; half++) {
+            const uint32_t id = half ? b : a;
+            if (id == PSIM_NONE) continue;
+            uint32_t s = gm_hash(id);
+            for (uint32_t t = 0; t < GM_TAB; t++, s = (s + 1) % GM_TAB)      // (ends at a free slot: <= 128 ids)
+                if (atomicCAS(&tab[s], PSIM_NONE, id) == PSIM_NONE) break;
+        }
+    }
+    __syncthreads();
+    uint32_t c = 0;
+    if (k >= 2) {
+        for (uint32_t t = 0; t < k; t++) {                                   // (uniform)
+            const uint32_t p = t < 64 ? shfl(a, (int)t) : shfl(b, (int)(t - 64));
+            uint32_t x, y;
+            sh_row_load(adj + off[p], min((uint32_t)cnt[p], (uint32_t)PSIM_SVIEW_CAP), x, y);
+            for (int half = 0; half < 2; half++) {
+                const uint32_t id = half ? y : x;
+                if (id == PSIM_NONE) continue;
+                uint32_t s = gm_hash(id);
+                for (uint32_t u = 0; u < GM_TAB; u++, s = (s + 1) % GM_TAB) {
+                    const uint32_t v = tab[s];
+                    if (v == id) c++;
+                    if (v == id || v == PSIM_NONE) break;
+                }
+            }
+        }
+        c = sh_wave_sum(c);
+    }
+    if (up && l == 0) gm_cluster_add(sh, k, c);
+    __syncthreads();
+    if (threadIdx.x < GM_N && sh[threadIdx.x]) atomicAdd(&gm[threadIdx.x], sh[threadIdx.x]);
+}
+
+// source slot j starts at sources[j] if that node is live; live: the mask of
+// such slots (one block of 64 threads; the sources are distinct and < n)
+__global__ void k_gm_init(const uint32_t* __restrict__ sources, uint32_t ns, const uint8_t* __restrict__ flags,
+                          unsigned long long* seen, unsigned long long* front, unsigned long long* live) {
+    const uint32_t j = threadIdx.x;
+    const bool on = j < ns && (flags[sources[j]] & F_UP);
+    if (on) { seen[sources[j]] = 1ull << j; front[sources[j]] = 1ull << j; }
+    const uint64_t m = ballot(on);
+    if (j == 0) *live = m;
+}
+
+// a node on the frontier ORs its word into each out-neighbour that lacks a bit of it
+__global__ void k_gm_push(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
+                          const uint32_t* __restrict__ adj, uint32_t n,
+                          const unsigned long long* __restrict__ front,
+                          const unsigned long long* __restrict__ seen, unsigned long long* next) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long f = front[i];
+    if (!f) return;
+    const uint32_t* row = adj + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP);
+    for (uint32_t k = 0, c = cnt[i]; k < c; k++) {
+        const uint32_t p = row[k];
+        if (f & ~seen[p]) atomicOr(&next[p], f);
+    }
+}
+
+// the level's new bits: into seen, the next frontier, lv[0] (their OR over
+// all nodes), lv[1] (their number) and reach[j] per slot; reduced in the wave,
+// then in the block's LDS, and only where a wave saw a new bit
+__global__ void __launch_bounds__(BLK) k_gm_level(uint32_t n, unsigned long long* next, unsigned long long* seen,
+                                                  unsigned long long* front, unsigned long long* lv,
+                                                  unsigned long long* reach) {
+    __shared__ unsigned long long sh_reach[PSIM_GRAPH_SOURCES], sh_lv[2];
+    if (threadIdx.x < PSIM_GRAPH_SOURCES) sh_reach[threadIdx.x] = 0;
+    if (threadIdx.x < 2) sh_lv[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long nw = 0;
+    if (i < n) {
+        const unsigned long long nx = next[i];
+        if (nx) {
+            const unsigned long long s = seen[i];
+            nw = nx & ~s;
+            next[i] = 0;
+            if (nw) seen[i] = s | nw;
+        }
+        if (front[i] != nw) front[i] = nw;
+    }
+    if (ballot(nw != 0)) {                            // (uniform)
+        uint32_t lo = (uint32_t)nw, hi = (uint32_t)(nw >> 32);
+        for (int d = 32; d; d >>= 1) { lo |= (uint32_t)__shfl_xor((int)lo, d); hi |= (uint32_t)__shfl_xor((int)hi, d); }
+        const uint32_t cnt = sh_wave_sum(popc(nw));
+        uint64_t todo = ((uint64_t)hi << 32) | lo;
+        if (lane_id() == 0) { atomicOr(&sh_lv[0], (unsigned long long)todo); atomicAdd(&sh_lv[1], (unsigned long long)cnt); }
+        while (todo) {
+            const int j = ffs64(todo);
+            todo &= todo - 1;
+            const uint32_t c = popc(ballot((nw >> j) & 1));
+            if (lane_id() == 0) atomicAdd(&sh_reach[j], (unsigned long long)c);
+        }
+    }
+    __syncthreads();
+    if (!sh_lv[0]) return;                            // (uniform per block)
+    if (threadIdx.x < PSIM_GRAPH_SOURCES && sh_reach[threadIdx.x]) atomicAdd(&reach[threadIdx.x], sh_reach[threadIdx.x]);
+    if (threadIdx.x == 0) { atomicOr(&lv[0], sh_lv[0]); atomicAdd(&lv[1], sh_lv[1]); }
+}
+
 // ------------------------------------------------------------- buffers --
 template <typename T>
 struct DBuf {
@@ -5181,6 +5382,27 @@ static int cc_run(const uint32_t* off, const uint8_t* rn, const uint32_t* adj, c
     return PSIM_OK;
 }
 
+// the whole overlay's active rows by global id, gact (PSIM_ACTIVE_CAP ids a
+// row) and gan (their lengths), of per * G rows: the shards' rows are gathered
+// (device copies for virtual shards, an in-place ncclAllGather of equal
+// per-rank slots for RCCL ranks; 33 B per node), and every process then runs
+// the same kernels over the whole overlay
+static int gather_active_rows(psim_handle* h, hipStream_t st, TmpBuf<uint32_t>& gact, TmpBuf<uint8_t>& gan) {
+    const uint32_t per = h->per;
+    const size_t npad = (size_t)per * h->G;
+    TRY(gact.alloc_on(npad * PSIM_ACTIVE_CAP, st)); TRY(gan.alloc_on(npad, st));
+    for (Shard* s : h->shards)
+        if (s->n)
+            k_pack_act<<<grid_for(s->n), BLK, 0, st>>>(s->hdr.p, s->act.p, s->n,
+                                                       gact.p + (size_t)s->lo * PSIM_ACTIVE_CAP, gan.p + s->lo);
+    if (h->ranked) {
+        const size_t off = (size_t)h->rank * per;
+        TRY(h->comm->all_gather(gact.p + off * PSIM_ACTIVE_CAP, gact.p, (size_t)per * PSIM_ACTIVE_CAP * 4, st));
+        TRY(h->comm->all_gather(gan.p + off, gan.p, per, st));
+    }
+    return PSIM_OK;
+}
+
 int psim_get_histograms(psim_handle* h, psim_histograms* out) {
     if (!h || !out) return PSIM_EINVAL;
     if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE || h->hosted) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
@@ -5226,26 +5448,12 @@ int psim_get_histograms(psim_handle* h, psim_histograms* out) {
     out->n_up = hv[H_NUP]; out->delivered = hv[H_DELIV]; out->last_round = hv[H_LAST];
     out->active_links = hv[H_LINKS];
     {
-        // symmetry and components need every node's active row: the shards'
-        // rows are gathered by global id (device copies for virtual shards,
-        // an in-place ncclAllGather of equal per-rank slots for RCCL ranks;
-        // 33 B per node), and every process then runs the same kernels over
-        // the whole overlay
-        const uint32_t per = h->per, n = h->N;
-        const size_t npad = (size_t)per * h->G;
+        // symmetry and components need every node's active row
+        const uint32_t n = h->N;
         TmpBuf<uint32_t> gact, L, sz, flag;
         TmpBuf<uint8_t> gan;
         TmpBuf<unsigned long long> r;
-        TRY(gact.alloc_on(npad * PSIM_ACTIVE_CAP, st)); TRY(gan.alloc_on(npad, st));
-        for (Shard* s : h->shards)
-            if (s->n)
-                k_pack_act<<<grid_for(s->n), BLK, 0, st>>>(s->hdr.p, s->act.p, s->n,
-                                                           gact.p + (size_t)s->lo * PSIM_ACTIVE_CAP, gan.p + s->lo);
-        if (h->ranked) {
-            const size_t off = (size_t)h->rank * per;
-            TRY(h->comm->all_gather(gact.p + off * PSIM_ACTIVE_CAP, gact.p, (size_t)per * PSIM_ACTIVE_CAP * 4, st));
-            TRY(h->comm->all_gather(gan.p + off, gan.p, per, st));
-        }
+        TRY(gather_active_rows(h, st, gact, gan));
         const uint8_t* fl = s0->flags.p;         // replicated: every shard holds all N
         TRY(L.alloc_on(n, st)); TRY(sz.alloc_on(n, st)); TRY(flag.alloc_on(1, st)); TRY(r.alloc_on(3, st));
         k_hist_sym<<<grid_for(n), BLK, 0, st>>>(gan.p, gact.p, fl, n, r.p);
@@ -5282,31 +5490,32 @@ static int strategy_hist_full(psim_handle* h, psim_strategy_histograms* out) {
     return PSIM_OK;
 }
 
-int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) {
-    if (!h || !out) return PSIM_EINVAL;
-    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE || h->hosted) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
-    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
-    memset(out, 0, sizeof *out);
-    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
-    if (h->cfg.strategy == PSIM_STRATEGY_FULL) return strategy_hist_full(h, out);
+// the compact CSR of a SCAMP handle's overlay, the same on every rank: node
+// i's cnt[i] links at adj + off[i] (ids by equal per-shard slots, per * G of
+// them; the pad ids hold no links)
+struct ShCsr {
+    TmpBuf<uint8_t> cnt;
+    TmpBuf<uint32_t> off, base, adj;
+    TmpBuf<unsigned long long> tot;
+};
+// sl: the SL_N words the count pass adds its per-node statistics to
+static int sh_build_csr(psim_handle* h, hipStream_t st, unsigned long long* sl, ShCsr& c) {
     Shard* s0 = h->shards[0];
-    hipStream_t st = s0->stream;
     const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
     const uint32_t N = h->N, per = h->per, v2 = h->cfg.strategy == PSIM_STRATEGY_SCAMP_V2 ? 1u : 0u;
-    const uint32_t npad = per * h->G;            // ids by equal per-shard slots (the pad ids hold no links)
+    const uint32_t npad = per * h->G;
     const uint32_t W = h->ranked ? (uint32_t)h->world : 1u, rper = h->ranked ? per : npad;
     auto rows_grid = [](uint32_t n) { return (n + SH_NPB - 1) / SH_NPB; };
-    // temporaries: O(N) bytes and words, and the links
-    TmpBuf<unsigned long long> sl, sg, tot;
-    TmpBuf<uint8_t> cnt;
-    TmpBuf<uint32_t> off, base, adj, indeg, L, sz, flag;
-    TRY(sl.alloc_on(SL_N, st)); TRY(sg.alloc_on(SG_N, st)); TRY(tot.alloc_on(1, st));
+    TmpBuf<uint8_t>& cnt = c.cnt;
+    TmpBuf<uint32_t>& off = c.off, & base = c.base, & adj = c.adj;
+    TmpBuf<unsigned long long>& tot = c.tot;
+    TRY(tot.alloc_on(1, st));
     TRY(cnt.alloc_on((size_t)npad + 1, st)); TRY(off.alloc_on((size_t)npad + 1, st)); TRY(base.alloc_on(W, st));
     // 1. the row pass: per-node statistics, and the link count of every node
     for (Shard* s : h->shards)
         if (s->n)
             k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, cnt.p, nullptr,
-                                                       nullptr, sl.p);
+                                                       nullptr, sl);
     HIP_TRY(hipGetLastError());
     if (h->ranked) TRY(h->comm->all_gather(cnt.p + (size_t)h->rank * per, cnt.p, per, st));
     // 2. row offsets: a scan of all counts (entry npad: the total); a rank's
@@ -5324,9 +5533,33 @@ int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) 
     for (Shard* s : h->shards)
         if (s->n)
             k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, cnt.p, off.p,
-                                                       adj.p, sl.p);
+                                                       adj.p, sl);
     HIP_TRY(hipGetLastError());
     if (h->ranked && slot) TRY(h->comm->all_gather(adj.p + (size_t)h->rank * slot, adj.p, (size_t)slot * 4, st));
+    return PSIM_OK;
+}
+
+int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) {
+    if (!h || !out) return PSIM_EINVAL;
+    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE || h->hosted) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    memset(out, 0, sizeof *out);
+    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
+    if (h->cfg.strategy == PSIM_STRATEGY_FULL) return strategy_hist_full(h, out);
+    Shard* s0 = h->shards[0];
+    hipStream_t st = s0->stream;
+    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
+    const uint32_t N = h->N, v2 = h->cfg.strategy == PSIM_STRATEGY_SCAMP_V2 ? 1u : 0u;
+    auto rows_grid = [](uint32_t n) { return (n + SH_NPB - 1) / SH_NPB; };
+    // temporaries: O(N) bytes and words, and the links
+    TmpBuf<unsigned long long> sl, sg;
+    TmpBuf<uint32_t> indeg, L, sz, flag;
+    ShCsr csr;
+    TmpBuf<uint8_t>& cnt = csr.cnt;
+    TmpBuf<uint32_t>& off = csr.off, & adj = csr.adj;
+    TRY(sl.alloc_on(SL_N, st)); TRY(sg.alloc_on(SG_N, st));
+    // 1., 2. the row pass and the CSR
+    TRY(sh_build_csr(h, st, sl.p, csr));
     // 3. over the whole CSR (every rank the same): in-degrees, reciprocity,
     // components; the in_view rows are local and probe it
     TRY(indeg.alloc_on(N, st)); TRY(L.alloc_on(N, st)); TRY(sz.alloc_on(N, st)); TRY(flag.alloc_on(1, st));
@@ -5358,6 +5591,99 @@ int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) 
     out->in_view_links = lv[SL_IVL]; out->in_view_confirmed = lv[SL_IVC];
     out->links = gv[SG_LINKS]; out->mutual_links = gv[SG_MUTUAL]; out->in_degree_max = gv[SG_INMAX];
     out->isolated = gv[SG_ISOL]; out->components = gv[SG_COMPS]; out->largest_component = gv[SG_LARGEST];
+    return PSIM_OK;
+}
+
+int psim_get_graph_metrics(psim_handle* h, const uint32_t* sources, size_t n_sources, uint32_t max_levels,
+                           psim_graph_metrics* out) {
+    static_assert(PSIM_GRAPH_SOURCES == 64, "one bit of a 64-bit word per source slot");
+    if (!h || !out || (n_sources && !sources) || n_sources > PSIM_GRAPH_SOURCES) return PSIM_EINVAL;
+    const bool pl = h->cfg.manager == PSIM_MANAGER_PLUGGABLE;
+    if (h->hosted || (pl && h->cfg.strategy == PSIM_STRATEGY_FULL)) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
+    if (h->round_open) return PSIM_ESTATE;
+    const uint32_t N = h->N, ns = (uint32_t)n_sources;
+    uint32_t src[PSIM_GRAPH_SOURCES] = {0};
+    for (uint32_t j = 0; j < ns; j++) {
+        if (sources[j] >= N) return PSIM_ERANGE;
+        src[j] = sources[j];
+    }
+    for (uint32_t j = 0; j < ns; j++)
+        for (uint32_t q = 0; q < j; q++)
+            if (src[q] == src[j]) return PSIM_EINVAL;
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    memset(out, 0, sizeof *out);
+    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
+    Shard* s0 = h->shards[0];
+    hipStream_t st = s0->stream;
+    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
+    // 1. the link set as rows, the same on every rank: the SCAMP CSR, or
+    // HyParView's gathered rows filtered once (p != i, p live), so that both
+    // halves read the same L
+    ShCsr csr;
+    TmpBuf<unsigned long long> sl, gm;
+    TmpBuf<uint32_t> gact, fadj;
+    TmpBuf<uint8_t> gan, fcnt;
+    const uint32_t* off = nullptr;
+    const uint32_t* adj = nullptr;
+    const uint8_t* cnt = nullptr;
+    TRY(gm.alloc_on(GM_N, st));
+    if (pl) {
+        TRY(sl.alloc_on(SL_N, st));              // (the count pass's statistics: not reported here)
+        TRY(sh_build_csr(h, st, sl.p, csr));
+        off = csr.off.p; adj = csr.adj.p; cnt = csr.cnt.p;
+    } else {
+        TRY(gather_active_rows(h, st, gact, gan));
+        TRY(fadj.alloc_on((size_t)N * PSIM_ACTIVE_CAP, st)); TRY(fcnt.alloc_on(N, st));
+        k_gm_filter<<<grid_for(N), BLK, 0, st>>>(gan.p, gact.p, fl, N, fadj.p, fcnt.p);
+        adj = fadj.p; cnt = fcnt.p;
+    }
+    // 2. clustering
+    if (pl) k_gm_cluster<<<(N + BLK / 64 - 1) / (BLK / 64), BLK, 0, st>>>(off, cnt, adj, fl, N, gm.p);
+    else k_gm_cluster_hv<<<grid_for((uint64_t)N * PSIM_ACTIVE_CAP), BLK, 0, st>>>(cnt, adj, fl, N, gm.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long gv[GM_N];
+    HIP_TRY(hipMemcpyAsync(gv, gm.p, sizeof gv, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->n_up = gv[GM_NUP]; out->links = gv[GM_LINKS]; out->cl_nodes = gv[GM_NODES];
+    out->cl_closed = gv[GM_CLOSED]; out->cl_pairs = gv[GM_PAIRS]; out->cl_sum_q32 = gv[GM_Q32];
+    if (!ns) return PSIM_OK;
+    // 3. the BFS: a push and a level kernel per level, the level's words read
+    // back after each (zero new bits end it), at most `cap` levels
+    const uint32_t cap = !max_levels || max_levels > PSIM_GRAPH_MAX_LEVELS ? PSIM_GRAPH_MAX_LEVELS : max_levels;
+    TmpBuf<uint32_t> dsrc;
+    TmpBuf<unsigned long long> seen, front, next, lv, reach;
+    TRY(dsrc.alloc_on(PSIM_GRAPH_SOURCES, st));
+    TRY(seen.alloc_on(N, st)); TRY(front.alloc_on(N, st)); TRY(next.alloc_on(N, st));
+    TRY(lv.alloc_on(2 * ((size_t)cap + 1), st)); TRY(reach.alloc_on(PSIM_GRAPH_SOURCES, st));
+    HIP_TRY(hipMemcpyAsync(dsrc.p, src, sizeof src, hipMemcpyHostToDevice, st));
+    k_gm_init<<<1, 64, 0, st>>>(dsrc.p, ns, fl, seen.p, front.p, lv.p);      // (lv[0]: the live slots)
+    unsigned long long live = 0;
+    HIP_TRY(hipMemcpyAsync(&live, lv.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->sources_live = (uint64_t)__builtin_popcountll(live);
+    if (!live) return PSIM_OK;
+    for (uint32_t d = 1; d <= cap; d++) {
+        unsigned long long w[2] = {0, 0};
+        k_gm_push<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, N, front.p, seen.p, next.p);
+        k_gm_level<<<grid_for(N), BLK, 0, st>>>(N, next.p, seen.p, front.p, lv.p + 2 * (size_t)d, reach.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(w, lv.p + 2 * (size_t)d, sizeof w, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        out->levels = d;
+        if (!w[0]) break;
+        out->dist[d < PSIM_HIST_BINS ? d : PSIM_HIST_BINS - 1] += w[1];
+        out->dist_sum += (uint64_t)d * w[1];
+        out->pairs_reached += w[1];
+        for (uint32_t j = 0; j < PSIM_GRAPH_SOURCES; j++)
+            if ((w[0] >> j) & 1) out->ecc[j] = d;
+        out->ecc_max = d;
+        if (d == cap) out->truncated = 1;
+    }
+    unsigned long long rv[PSIM_GRAPH_SOURCES];
+    HIP_TRY(hipMemcpyAsync(rv, reach.p, sizeof rv, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t j = 0; j < PSIM_GRAPH_SOURCES; j++) out->reach[j] = rv[j];
+    out->pairs_unreached = out->sources_live * (out->n_up - 1) - out->pairs_reached;
     return PSIM_OK;
 }
 

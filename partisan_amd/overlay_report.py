@@ -3,7 +3,9 @@
 (workloads.doubling_join(N, seed)) plus `--settle` rounds to the same round,
 then the device statistics of each -- histograms() and
 strategy_histograms() -- go into one JSON file and one Markdown table:
-in-degree histograms, view fill, links and reciprocity, components.
+in-degree histograms, view fill, links and reciprocity, components, and from
+graph_metrics() the clustering coefficient and the shortest paths from 64
+seeded sources.
 
     python -m partisan_amd.overlay_report --nodes N --seed S [--out DIR]
 """
@@ -40,17 +42,31 @@ def _run(cfg, sched, until):
         t1 = time.time()
         h = sim.histograms() if cfg.manager == 0 else sim.strategy_histograms()
         t2 = time.time()
+        g = sim.graph_metrics(seed=cfg.seed)
+        t3 = time.time()
         rounds = int(sim.round)
-    return h, {"rounds": rounds, "messages": int(st["emitted"].sum()), "overflow": int(st["overflow"].sum()),
-               "run_s": round(t1 - t0, 3), "stats_s": round(t2 - t1, 3)}
+    return h, g, {"rounds": rounds, "messages": int(st["emitted"].sum()), "overflow": int(st["overflow"].sum()),
+                  "run_s": round(t1 - t0, 3), "stats_s": round(t2 - t1, 3), "graph_s": round(t3 - t2, 3)}
+
+
+def _graph(g):
+    """the report's keys from a graph_metrics() dict: the mean local
+    clustering coefficient over all live nodes (a node with fewer than two
+    neighbours counts 0), and the path lengths from the 64 seeded sources"""
+    return {
+        "clustering_mean": g["cl_sum_q32"] / 2.0 ** 32 / g["n_up"] if g["n_up"] else 0.0,
+        "path_mean": g["dist_sum"] / g["pairs_reached"] if g["pairs_reached"] else 0.0,
+        "path_max": g["ecc_max"], "pairs_unreached": g["pairs_unreached"],
+        "path_sources": g["sources_live"], "path_levels": g["levels"],
+    }
 
 
 def build(n, seed, settle=SETTLE, device=-1):
     sched = W.doubling_join(n, seed)
     until = sched[-1][0] + 1 + settle
-    hv, hv_run = _run(default_config(n_nodes=n, seed=seed, device=device), sched, until)
-    sc, sc_run = _run(default_config(n_nodes=n, seed=seed, manager=1, strategy=2, scamp_c=5, device=device),
-                      sched, until)
+    hv, hv_g, hv_run = _run(default_config(n_nodes=n, seed=seed, device=device), sched, until)
+    sc, sc_g, sc_run = _run(default_config(n_nodes=n, seed=seed, manager=1, strategy=2, scamp_c=5, device=device),
+                            sched, until)
     up_h, up_s = hv["n_up"], sc["n_up"]
     hyparview = {
         "n_up": up_h, **hv_run,
@@ -60,6 +76,7 @@ def build(n, seed, settle=SETTLE, device=-1):
         "links": hv["active_links"], "mutual_links": hv["symmetric_links"],
         "reciprocity": hv["symmetric_links"] / hv["active_links"] if hv["active_links"] else 0.0,
         "components": hv["components"], "largest_component": hv["largest_component"],
+        **_graph(hv_g),
     }
     scamp = {
         "n_up": up_s, **sc_run,
@@ -75,6 +92,7 @@ def build(n, seed, settle=SETTLE, device=-1):
         "duplicate_entries": sc["duplicate_entries"],
         "in_view_links": sc["in_view_links"], "in_view_confirmed": sc["in_view_confirmed"],
         "components": sc["components"], "largest_component": sc["largest_component"], "isolated": sc["isolated"],
+        **_graph(sc_g),
     }
     return {"config": "D", "nodes": n, "seed": seed, "settle_rounds": settle, "round": until,
             "hyparview": hyparview, "scamp_v2": scamp}
@@ -96,6 +114,12 @@ def markdown(rep):
         ("components", a["components"], b["components"]),
         ("largest component", a["largest_component"], b["largest_component"]),
         ("statistics call (s)", a["stats_s"], b["stats_s"]),
+        ("clustering_mean (local clustering coefficient, mean over live nodes)", f"{a['clustering_mean']:.6f}",
+         f"{b['clustering_mean']:.6f}"),
+        (f"path_mean (shortest paths from {a['path_sources']} / {b['path_sources']} sources, reached pairs)",
+         f"{a['path_mean']:.3f}", f"{b['path_mean']:.3f}"),
+        ("path_max (longest shortest path seen; pairs not reached)", f"{a['path_max']} ({a['pairs_unreached']})",
+         f"{b['path_max']} ({b['pairs_unreached']})"),
     ]
     out = [f"# HyParView and SCAMP v2 at {rep['nodes']} nodes (seed {rep['seed']}, round {rep['round']})", "",
            "| | HyParView | SCAMP v2 (c = 5) |", "|---|---|---|"]

@@ -389,6 +389,53 @@ class Simulator(_Driver):
             out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
         return out
 
+    def graph_metrics(self, sources=None, k=64, seed=0, max_levels=0):
+        """Path lengths from up to 64 sources and the clustering of the whole
+        overlay (psim_graph_metrics) as a dict of ints / arrays; a collective
+        on rank handles.  sources=None draws k distinct ids from
+        np.random.Generator(PCG64([seed, 0x6d])); an empty list fills the
+        clustering half only."""
+        if sources is None:
+            rng = np.random.Generator(np.random.PCG64([seed, 0x6d]))
+            sources = rng.choice(self.n, size=min(k, self.n), replace=False)
+        src = np.ascontiguousarray(sources, np.uint32).reshape(-1)
+        m = _abi.PsimGraphMetrics()
+        self._check(self._extra["get_graph_metrics"](self._h, _abi.u32p(src) if src.size else None, src.size,
+                                                     max_levels, C.byref(m)), "get_graph_metrics")
+        out = {}
+        for name, _ in _abi.PsimGraphMetrics._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(m, name)
+            out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
+        return out
+
+    # the fields of graph_metrics() that add up over disjoint source batches
+    _PATH_SUMS = ("sources_live", "dist", "dist_sum", "pairs_reached", "pairs_unreached")
+
+    def graph_metrics_all(self, max_levels=0):
+        """graph_metrics() over every id as a source, in batches of 64: exact
+        all-pairs path numbers of a small overlay.  The path sums add up over
+        the batches; ecc_max, levels and truncated are the largest; `reach`
+        and `ecc` come back per node (n entries, zero for a dead node)."""
+        out = None
+        reach, ecc = np.zeros(self.n, np.uint64), np.zeros(self.n, np.uint64)
+        for lo in range(0, self.n, _abi.GRAPH_SOURCES):
+            ids = np.arange(lo, min(self.n, lo + _abi.GRAPH_SOURCES), dtype=np.uint32)
+            m = self.graph_metrics(ids, max_levels=max_levels)
+            reach[ids], ecc[ids] = m["reach"][: ids.size], m["ecc"][: ids.size]
+            if out is None:
+                out = m
+                continue
+            for f in self._PATH_SUMS:
+                out[f] = out[f] + m[f]
+            for f in ("ecc_max", "levels", "truncated"):
+                out[f] = max(out[f], m[f])
+        if out is None:
+            out = self.graph_metrics([])
+        out["reach"], out["ecc"] = reach, ecc
+        return out
+
     # (k_node_prep: the quiet lazy ticks it counts without running the node)
     KERNELS = ("k_relay", "k_shuf", "k_lite_half", "k_consume", "k_ptl", "k_pt", "k_node_prep")
 
