@@ -56,9 +56,31 @@ static int get_u32(ErlNifEnv *env, ERL_NIF_TERM map, const char *k, uint32_t *ou
     return 1;
 }
 
-/* create(#{n_nodes => N, seed => S, max_active_size => .., ...,
+/* An id array out of binary data.  A binary's data -- a sub-binary's above
+ * all, and pack/1's results may be such -- need not be 4-byte aligned, so the
+ * ids are copied into an aligned buffer (enif_free it); NULL: out of memory. */
+static uint32_t *ids_copy(const ErlNifBinary *b) {
+    uint32_t *p = enif_alloc(b->size ? b->size : 4);
+    if (p) memcpy(p, b->data, b->size);
+    return p;
+}
+
+/* the same for two arrays of one size in one buffer: the second starts at p + size / 4 */
+static uint32_t *ids_copy2(const ErlNifBinary *a, const ErlNifBinary *b) {
+    uint32_t *p = enif_alloc(a->size ? 2 * a->size : 4);
+    if (p) { memcpy(p, a->data, a->size); memcpy(p + a->size / 4, b->data, b->size); }
+    return p;
+}
+
+/* create(#{n_nodes => N, seed => S, max_active_size => .., min_active_size => ..,
+ *         max_passive_size => .., arwl => .., prwl => .., k_active => .., k_passive => ..,
+ *         shuffle_period => Rounds, promotion_period => Rounds, random_promotion => 0 | 1,
+ *         persist_epoch => 0 | 1, plumtree => 0 | 1, lazy_tick_period => Rounds,
  *         manager => 0 | 1 | 2, strategy => 0 | 1 | 2, fanout => K, scamp_c => C,
- *         periodic_interval => Rounds, xbot_period => Rounds}) -> {ok, Ref}
+ *         periodic_interval => Rounds, strict => 0 | 1, xbot_period => Rounds}) -> {ok, Ref}
+ * Every protocol field of psim_config has its key; a key left out keeps
+ * psim_default_config's value; the argument must be a map and every key
+ * present an unsigned integer (seed: up to 64 bits), else badarg.
  * manager 1 = the pluggable manager with strategy 0 full, 1 scamp v1, 2 scamp v2;
  * manager 2 = partisan_hyparview_xbot_peer_service_manager (X-BOT);
  * host_lo => Lo, host_hi => Hi: a host-exchange handle that simulates the ids
@@ -68,13 +90,20 @@ static ERL_NIF_TERM nif_create(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv
     ErlNifUInt64 seed;
     ERL_NIF_TERM v;
     psim_default_config(&c);
+    /* (get_u32 keeps the default when the lookup fails, which it also does on a term that is no map) */
+    if (!enif_is_map(env, argv[0])) return enif_make_badarg(env);
     if (!get_u32(env, argv[0], "n_nodes", &c.n_nodes) ||
         !get_u32(env, argv[0], "max_active_size", &c.max_active_size) ||
         !get_u32(env, argv[0], "min_active_size", &c.min_active_size) ||
         !get_u32(env, argv[0], "max_passive_size", &c.max_passive_size) ||
         !get_u32(env, argv[0], "arwl", &c.arwl) || !get_u32(env, argv[0], "prwl", &c.prwl) ||
+        !get_u32(env, argv[0], "k_active", &c.k_active) || !get_u32(env, argv[0], "k_passive", &c.k_passive) ||
         !get_u32(env, argv[0], "shuffle_period", &c.shuffle_period) ||
+        !get_u32(env, argv[0], "promotion_period", &c.promotion_period) ||
+        !get_u32(env, argv[0], "random_promotion", &c.random_promotion) ||
+        !get_u32(env, argv[0], "persist_epoch", &c.persist_epoch) ||
         !get_u32(env, argv[0], "plumtree", &c.plumtree) ||
+        !get_u32(env, argv[0], "lazy_tick_period", &c.lazy_tick_period) ||
         !get_u32(env, argv[0], "manager", &c.manager) ||
         !get_u32(env, argv[0], "strategy", &c.strategy) ||
         !get_u32(env, argv[0], "fanout", &c.fanout) || !get_u32(env, argv[0], "strict", &c.strict) ||
@@ -82,9 +111,10 @@ static ERL_NIF_TERM nif_create(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv
         !get_u32(env, argv[0], "periodic_interval", &c.periodic_interval) ||
         !get_u32(env, argv[0], "xbot_period", &c.xbot_period))
         return enif_make_badarg(env);
-    if (enif_get_map_value(env, argv[0], enif_make_atom(env, "seed"), &v) &&
-        enif_get_uint64(env, v, &seed))
+    if (enif_get_map_value(env, argv[0], enif_make_atom(env, "seed"), &v)) {
+        if (!enif_get_uint64(env, v, &seed)) return enif_make_badarg(env);
         c.seed = seed;
+    }
     uint32_t host_lo = 0, host_hi = 0;
     uint32_t host_id[64];                 /* (psim_create reads the id, it does not keep the pointer) */
     if (!get_u32(env, argv[0], "host_lo", &host_lo) || !get_u32(env, argv[0], "host_hi", &host_hi))
@@ -96,7 +126,10 @@ static ERL_NIF_TERM nif_create(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv
         c.comm_id = host_id;
     }
     sim_res *r = enif_alloc_resource(SIM_RT, sizeof *r);
+    if (!r) return err(env, PSIM_ENOMEM);
+    r->h = NULL;                          /* (sim_dtor reads both) */
     r->mu = enif_mutex_create("psim");
+    if (!r->mu) { enif_release_resource(r); return err(env, PSIM_ENOMEM); }
     r->n_nodes = c.n_nodes;
     int rc = psim_create(&c, &r->h);
     if (rc) { r->h = NULL; enif_release_resource(r); return err(env, rc); }
@@ -112,9 +145,12 @@ static ERL_NIF_TERM nif_join(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]
         !enif_inspect_binary(env, argv[1], &a) || !enif_inspect_binary(env, argv[2], &b) ||
         a.size != b.size || a.size % 4)
         return enif_make_badarg(env);
-    LOCK_OR_BUSY(r);
-    int rc = psim_join(r->h, (const uint32_t *)a.data, (const uint32_t *)b.data, a.size / 4);
+    uint32_t *ids = ids_copy2(&a, &b);
+    if (!ids) return err(env, PSIM_ENOMEM);
+    LOCK_OR_BUSY_FREE(r, ids);
+    int rc = psim_join(r->h, ids, ids + a.size / 4, a.size / 4);
     enif_mutex_unlock(r->mu);
+    enif_free(ids);
     return rc ? err(env, rc) : enif_make_atom(env, "ok");
 }
 
@@ -123,9 +159,12 @@ static ERL_NIF_TERM nif_crash(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[
     if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r) ||
         !enif_inspect_binary(env, argv[1], &a) || a.size % 4)
         return enif_make_badarg(env);
-    LOCK_OR_BUSY(r);
-    int rc = psim_crash(r->h, (const uint32_t *)a.data, a.size / 4);
+    uint32_t *ids = ids_copy(&a);
+    if (!ids) return err(env, PSIM_ENOMEM);
+    LOCK_OR_BUSY_FREE(r, ids);
+    int rc = psim_crash(r->h, ids, a.size / 4);
     enif_mutex_unlock(r->mu);
+    enif_free(ids);
     return rc ? err(env, rc) : enif_make_atom(env, "ok");
 }
 
@@ -135,9 +174,12 @@ static ERL_NIF_TERM nif_revive(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv
     if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r) ||
         !enif_inspect_binary(env, argv[1], &a) || a.size % 4)
         return enif_make_badarg(env);
-    LOCK_OR_BUSY(r);
-    int rc = psim_revive(r->h, (const uint32_t *)a.data, a.size / 4);
+    uint32_t *ids = ids_copy(&a);
+    if (!ids) return err(env, PSIM_ENOMEM);
+    LOCK_OR_BUSY_FREE(r, ids);
+    int rc = psim_revive(r->h, ids, a.size / 4);
     enif_mutex_unlock(r->mu);
+    enif_free(ids);
     return rc ? err(env, rc) : enif_make_atom(env, "ok");
 }
 
@@ -147,9 +189,12 @@ static ERL_NIF_TERM nif_leave(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[
     if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r) ||
         !enif_inspect_binary(env, argv[1], &a) || a.size % 4)
         return enif_make_badarg(env);
-    LOCK_OR_BUSY(r);
-    int rc = psim_leave(r->h, (const uint32_t *)a.data, a.size / 4);
+    uint32_t *ids = ids_copy(&a);
+    if (!ids) return err(env, PSIM_ENOMEM);
+    LOCK_OR_BUSY_FREE(r, ids);
+    int rc = psim_leave(r->h, ids, a.size / 4);
     enif_mutex_unlock(r->mu);
+    enif_free(ids);
     return rc ? err(env, rc) : enif_make_atom(env, "ok");
 }
 
@@ -160,9 +205,12 @@ static ERL_NIF_TERM nif_leave_node(ErlNifEnv *env, int argc, const ERL_NIF_TERM 
         !enif_inspect_binary(env, argv[1], &a) || !enif_inspect_binary(env, argv[2], &t) ||
         a.size % 4 || a.size != t.size)
         return enif_make_badarg(env);
-    LOCK_OR_BUSY(r);
-    int rc = psim_leave_node(r->h, (const uint32_t *)a.data, (const uint32_t *)t.data, a.size / 4);
+    uint32_t *ids = ids_copy2(&a, &t);
+    if (!ids) return err(env, PSIM_ENOMEM);
+    LOCK_OR_BUSY_FREE(r, ids);
+    int rc = psim_leave_node(r->h, ids, ids + a.size / 4, a.size / 4);
     enif_mutex_unlock(r->mu);
+    enif_free(ids);
     return rc ? err(env, rc) : enif_make_atom(env, "ok");
 }
 
@@ -205,9 +253,12 @@ static ERL_NIF_TERM nif_omission(ErlNifEnv *env, int argc, const ERL_NIF_TERM ar
         !enif_inspect_binary(env, argv[2], &a) || !enif_inspect_binary(env, argv[3], &b) ||
         !enif_get_int(env, argv[4], &on) || a.size % 4 || a.size != b.size)
         return enif_make_badarg(env);
-    LOCK_OR_BUSY(r);
-    int rc = psim_set_omission(r->h, kind, (const uint32_t *)a.data, (const uint32_t *)b.data, a.size / 4, on);
+    uint32_t *ids = ids_copy2(&a, &b);
+    if (!ids) return err(env, PSIM_ENOMEM);
+    LOCK_OR_BUSY_FREE(r, ids);
+    int rc = psim_set_omission(r->h, kind, ids, ids + a.size / 4, a.size / 4, on);
     enif_mutex_unlock(r->mu);
+    enif_free(ids);
     return rc ? err(env, rc) : enif_make_atom(env, "ok");
 }
 
@@ -217,9 +268,12 @@ static ERL_NIF_TERM nif_faulted(ErlNifEnv *env, int argc, const ERL_NIF_TERM arg
     if (!enif_get_resource(env, argv[0], SIM_RT, (void **)&r) || !enif_inspect_binary(env, argv[1], &a) ||
         !enif_get_int(env, argv[2], &on) || a.size % 4)
         return enif_make_badarg(env);
-    LOCK_OR_BUSY(r);
-    int rc = psim_set_faulted(r->h, (const uint32_t *)a.data, a.size / 4, on);
+    uint32_t *ids = ids_copy(&a);
+    if (!ids) return err(env, PSIM_ENOMEM);
+    LOCK_OR_BUSY_FREE(r, ids);
+    int rc = psim_set_faulted(r->h, ids, a.size / 4, on);
     enif_mutex_unlock(r->mu);
+    enif_free(ids);
     return rc ? err(env, rc) : enif_make_atom(env, "ok");
 }
 
@@ -240,6 +294,7 @@ static ERL_NIF_TERM nif_step(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]
         n == 0 || n > 100000)
         return enif_make_badarg(env);
     psim_round_stats *st = enif_alloc(n * sizeof *st);
+    if (!st) return err(env, PSIM_ENOMEM);
     enif_mutex_lock(r->mu);
     int rc = psim_step(r->h, n, st);
     enif_mutex_unlock(r->mu);
@@ -538,7 +593,7 @@ static ERL_NIF_TERM nif_set_phash_table(ErlNifEnv *env, int argc, const ERL_NIF_
     /* (binary data -- a sub-binary's above all -- need not be 4-byte
      * aligned: the hashes are copied into an aligned buffer first) */
     uint32_t *ph = enif_alloc(b.size ? b.size : 4);
-    if (!ph) return enif_make_badarg(env);
+    if (!ph) return err(env, PSIM_ENOMEM);
     memcpy(ph, b.data, b.size);
     LOCK_OR_BUSY_FREE(r, ph);
     int rc = psim_set_phash_table(r->h, ph, r->n_nodes);

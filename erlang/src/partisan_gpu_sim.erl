@@ -24,6 +24,14 @@ init() ->
            end,
     erlang:load_nif(filename:join(Priv, "partisan_gpu_sim_nif"), 0).
 
+%% Config: a map with a key for every protocol field of psim_config
+%% (include/partisan_gpu_sim.h) -- n_nodes, seed, max_active_size,
+%% min_active_size, max_passive_size, arwl, prwl, k_active, k_passive,
+%% shuffle_period, promotion_period, random_promotion, persist_epoch, plumtree,
+%% lazy_tick_period, manager, strategy, periodic_interval, scamp_c, fanout,
+%% strict, xbot_period -- and host_lo / host_hi for a host-exchange handle.  A
+%% key left out keeps the library's default.  Anything but a map, or a value
+%% that is no unsigned integer (seed: up to 64 bits, the others 32), is badarg.
 -spec create(map()) -> {ok, reference()} | {error, atom()}.
 create(_Config) -> erlang:nif_error(nif_not_loaded).
 

@@ -1745,7 +1745,7 @@ static void round_begin(struct psim_handle *h, psim_round_stats *st) {
 /* Round, second half: the messages addressed to the owned nodes (from every
  * shard) become the canonical inbox of round r+1, sorted by (dst, src, seq). */
 static void round_end(struct psim_handle *h, msgvec *in) {
-    qsort(in->v, in->n, sizeof(omsg), cmp_dst);
+    if (in->n) qsort(in->v, in->n, sizeof(omsg), cmp_dst);      /* (an empty vector's v is NULL) */
     if (h->fbits) {                 /* this round's snapshots are read next round */
         uint32_t *t = h->pay_in; h->pay_in = h->pay_out; h->pay_out = t;
         size_t tc = h->pay_in_cap; h->pay_in_cap = h->pay_out_cap; h->pay_out_cap = tc;

@@ -53,6 +53,7 @@ int enif_inspect_binary(ErlNifEnv *env, ERL_NIF_TERM bin_term, ErlNifBinary *bin
 int enif_get_int(ErlNifEnv *env, ERL_NIF_TERM term, int *ip);
 int enif_get_uint(ErlNifEnv *env, ERL_NIF_TERM term, unsigned *ip);
 int enif_get_uint64(ErlNifEnv *env, ERL_NIF_TERM term, ErlNifUInt64 *ip);
+int enif_is_map(ErlNifEnv *env, ERL_NIF_TERM term);
 int enif_get_map_value(ErlNifEnv *env, ERL_NIF_TERM map, ERL_NIF_TERM key, ERL_NIF_TERM *value);
 int enif_make_map_put(ErlNifEnv *env, ERL_NIF_TERM map_in, ERL_NIF_TERM key, ERL_NIF_TERM value,
                       ERL_NIF_TERM *map_out);
