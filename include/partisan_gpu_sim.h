@@ -214,7 +214,11 @@ typedef struct psim_config {
                                     ncclAllToAll, self ncclSend/ncclRecv, ncclAllReduce,
                                     ncclAllGather); an id from psim_host_comm_id: a
                                     host-exchange handle over part of the id space (below);
-                                    NULL = the in-place route */
+                                    NULL = the in-place route.  Every manager and strategy
+                                    runs over virtual shards and ranks, the full strategy
+                                    included (its STATE and GOSSIP records take the ORSet rows
+                                    they name along); a host-exchange
+                                    handle of the full strategy is PSIM_EUNSUPPORTED */
     uint64_t max_msgs_per_round; /* 0 = auto */
     /* pluggable manager */
     uint32_t manager;            /* PSIM_MANAGER_*, 0 = HyParView */
@@ -509,9 +513,12 @@ int psim_step(psim_handle *h, uint32_t n_rounds, psim_round_stats *stats);
 /* Inspection: views of nodes [first, first+count) into caller buffers. */
 int psim_get_nodes(psim_handle *h, uint32_t first, uint32_t count, psim_node_view *out);
 int psim_get_round(psim_handle *h, uint64_t *round);
-/* PLUGGABLE handles: strategy state of nodes [first, first+count) */
+/* PLUGGABLE handles: strategy state of nodes [first, first+count); as
+ * psim_get_nodes, a rank handle answers for the ids it owns (PSIM_ERANGE
+ * beyond them) */
 int psim_get_strategy_nodes(psim_handle *h, uint32_t first, uint32_t count, psim_strategy_view *out);
-/* full strategy: the member bitset of one node (bit j of word j/32 = node j) */
+/* full strategy: the member bitset of one node (bit j of word j/32 = node j);
+ * a rank handle answers for the ids it owns */
 int psim_get_member_bits(psim_handle *h, uint32_t node, uint32_t *words, size_t n_words);
 /* Delivery state of the tracked broadcast (the last psim_broadcast) at nodes
  * [first, first+count): have (0/1), first-delivery round and hop count
@@ -641,7 +648,11 @@ int psim_kernel_times(psim_handle *h, const char **names, double *ms, uint64_t *
  * ranks; this process's shards): *records = records sent to another shard,
  * *bytes = their bytes on the wire -- 32 B a record (dst, src, type word, seq,
  * a0-a2, word 7) plus 32 B for one with exchange ids (nex > 0), against 64 B
- * a record in memory.  Both 0 on one shard. */
+ * a record in memory.  A full-strategy handle adds the
+ * ORSet rows shipped with its STATE and GOSSIP records to *bytes: fw words a
+ * row (fw = ceil(n_nodes / 32) rounded up to 4), 2 fw once a leave/1 removal
+ * exists, one row per distinct (snapshot, destination shard) pair of a round.
+ * Both 0 on one shard. */
 int psim_get_exchange_stats(psim_handle *h, uint64_t *records, uint64_t *bytes);
 
 /* RCCL bootstrap for multi-process sharding (rank 0 creates, all pass it in cfg). */

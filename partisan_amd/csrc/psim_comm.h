@@ -1,10 +1,14 @@
 // psim_comm.h -- the collective layer of a multi-rank handle (shard_world >
 // 1, one shard per rank).  Every cross-rank step of the
 // engine goes through this interface:
-//   all_to_all_u64  the per-owner record counts of a round (exchange_rccl)
+//   all_to_all_u64  the per-owner record counts of a round (exchange_rccl); a
+//                   full-strategy handle: a second word per peer, the ORSet
+//                   rows that go with the records
 //   exchange        the records themselves, grouped point-to-point sends and
-//                   receives of byte ranges (exchange_rccl)
-//   all_reduce      the round's stats (sum), the overlay statistics (sum, max)
+//                   receives of byte ranges (exchange_rccl): per peer its
+//                   heads, its tails, and a full-strategy handle's rows
+//   all_reduce      the round's stats (sum), the overlay statistics (sum, max;
+//                   the full strategy's reference row: sum over its one owner)
 //   all_gather      the stop lists of leave/1, the active rows of the overlay
 //                   statistics
 // Two implementations:

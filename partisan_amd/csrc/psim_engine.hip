@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "psim_comm.h"
+#include "psim_payload.h"
 #include "psim_device.h"
 #include "psim_kernels.h"
 #include "psim_wave.h"
@@ -295,16 +296,26 @@ static_assert((1u << WSHIFT_MAX) * 16 <= 160 * 1024, "k_bucket_route: 16 W bytes
 // of the 64 cross xGMI.  A sender writes, per owner shard, the heads of its
 // records in (src, seq) order, then the tails in the same order, and puts a
 // long record's tail index (among that owner's tails) in the head's word 7
-// -- zero in every record that crosses shards: the full strategy's payload
-// slot lives there, and that strategy runs on one shard (psim_create).  The
-// receiver's heads and tails arrive in source-shard order; k_bucket_hist adds
-// the source's tail base to each long head's word 7, and k_bucket_route
-// gathers head + tail (or zeros) into the 64-B inbox record, word 7 zeroed.
+// -- zero in every other record but the full strategy's STATE and GOSSIP, whose
+// word 7 is a slot of the sender's snapshot arena (nex == 0 there: the two
+// uses never meet).  Such a record that crosses shards takes its rows along
+// as a third region per owner, after the heads and the tails, and its word 7
+// becomes the row's rank in that region (the payload exchange, below
+// k_owner_offsets).  The receiver's heads, tails and rows arrive in
+// source-shard order; k_bucket_hist adds the source's tail base to each long
+// head's word 7 -- and turns a payload head's rank into PAY_IMPORT | the
+// row's index among every imported row -- and k_bucket_route gathers head +
+// tail (or zeros) into the 64-B inbox record, a long record's word 7 zeroed.
 struct __attribute__((aligned(16))) Wire {
     uint4 q[2];
 };
 static_assert(sizeof(Wire) == 32, "a wire unit is half a record");
 __host__ __device__ __forceinline__ bool wire_long(uint32_t tt) { return ((tt >> 16) & 0xFFu) != 0u; }
+// the types whose word 7 names ORSet rows on a full-strategy handle (the payload exchange)
+__device__ __forceinline__ bool pay_type(uint32_t tt) {
+    const uint32_t t = tt & 0xFFu;
+    return t == PSIM_PL_STATE || t == PSIM_PL_GOSSIP;
+}
 
 // the sources of one route: the outbox runs of this shard's nodes (G == 1),
 // or the received heads and tails (G > 1)
@@ -326,6 +337,10 @@ struct RouteIn {
     // [g capT, ..); capH = 0: the packed layout above
     uint32_t capH, capT;
     uint32_t round;            // (the abort word's round, k_bucket_hist's header pass)
+    // dense, a sharded full-strategy handle: a STATE or GOSSIP head from
+    // another shard carries its row's rank among that source's payload rows
+    // (k_pay_rewrite); seg[2 (nseg + 1) + g] = source g's first imported row
+    uint32_t pay, self;
 };
 
 // The header of a batched rank round's message to one owner (XHDR wire
@@ -375,6 +390,10 @@ __device__ __forceinline__ void route_step(const RouteIn& in, uint32_t step, uin
             if (FIX && wire_long(h0.z)) {
                 if (in.capH) in.wire[i].q[1].w = min(in.wire[i].q[1].w, in.capT - 1) + g * in.capT;
                 else in.wire[i].q[1].w += in.seg[in.nseg + 1 + wire_source(in, i)];
+            }
+            if (FIX && in.pay && pay_type(h0.z)) {    // (full: no long records, no fixed layout)
+                const uint32_t src = wire_source(in, i);
+                if (src != in.self) in.wire[i].q[1].w = PAY_IMPORT | (in.wire[i].q[1].w + in.seg[2 * (in.nseg + 1) + src]);
             }
             f(i, h0.x - in.lo, in.pl ? 0u : max_emit(h0.z & 0xFF));
         }
@@ -837,7 +856,7 @@ constexpr uint32_t OO_THREADS = 1024;   // k_owner_offsets' block
 // stats summed from the count pass's tiles; and the round's span, its own
 // send counts (PIN_XCNT) and the outstanding pool's top into the pinned words
 __global__ void k_owner_offsets(const uint32_t* hoff, uint32_t nblk, uint32_t G, uint64_t* d_off, uint64_t* cnt,
-                                uint64_t* xw, uint32_t capH, uint32_t capT, uint32_t* ctl, uint32_t round,
+                                uint32_t cstride, uint64_t* xw, uint32_t capH, uint32_t capT, uint32_t* ctl, uint32_t round,
                                 uint32_t rank, Wire* sendbuf, StatsIn st) {
     __shared__ uint32_t smh, smt;
     __shared__ uint64_t ssum[64];
@@ -886,8 +905,8 @@ __global__ void k_owner_offsets(const uint32_t* hoff, uint32_t nblk, uint32_t G,
         return;
     }
     if (q <= 2 * G) d_off[q] = hoff[q * nblk];
-    if (cnt && q < G)
-        cnt[q] = dead ? 0ull
+    if (cnt && q < G)                                 // (cstride 2: k_pay_rank's row count beside it)
+        cnt[(size_t)q * cstride] = dead ? 0ull
                       : (uint64_t)(hoff[(q + 1) * nblk] - hoff[q * nblk]) |
                             ((uint64_t)(hoff[(G + q + 1) * nblk] - hoff[(G + q) * nblk]) << 32);
     if (!xw) return;                                  // (uniform)
@@ -904,6 +923,113 @@ __global__ void k_owner_offsets(const uint32_t* hoff, uint32_t nblk, uint32_t G,
     }
     __syncthreads();
     if (q < 128) xw[3 + q] = q == rank ? smh : q == 64 + rank ? smt : 0u;
+}
+
+// ------------------------------------------------ the payload exchange --
+// A full-strategy STATE or GOSSIP record names its ORSet rows by a slot of the
+// sender shard's snapshot arena (word 7).  With more than one shard or rank
+// the rows travel with the records that name them ("The
+// payload exchange"), after k_owner_part wrote the per-owner heads:
+//   k_pay_mark     bit (owner, slot) of a G x bw-word bitmap for every such
+//                  head addressed to another shard: a snapshot that k records
+//                  name for one owner is marked, and travels, once
+//   k_pay_rank     a block per owner: the popcount scan of its bitmap row --
+//                  the rank of a word's first row among the owner's rows, in
+//                  ascending slot order -- and the owner's row count
+//   k_pay_rewrite  each marked head's word 7 becomes its row's rank (records
+//                  of the full strategy have no tail, so the word is free)
+//   k_pay_list     once the host knows the counts: the slot of every row of
+//                  the payload send buffer, in (owner, rank) order
+//   k_pay_pack     a wave per row: row `slot` of the arena to row
+//                  (owner's first row + rank) of the payload send buffer, one
+//                  uint4 a lane; a row is fw words, 2 fw once removes exist
+// Records a shard sends to itself keep their slot.  The receiver's
+// k_bucket_hist turns a rank into PAY_IMPORT | (the source's first imported
+// row + rank), which k_consume_pl resolves against RoundArgs::pay_imp.
+constexpr uint32_t PP_BLK = 256;
+constexpr uint32_t PR_BLK = 1024;
+constexpr uint32_t PP_MAX_BLOCKS = 4096;            // k_pay_pack: grid-stride over the rows beyond
+
+template <bool REWRITE>
+__global__ void __launch_bounds__(PP_BLK) k_pay_mark(Wire* heads, const uint64_t* __restrict__ d_off, uint32_t G,
+                                                     uint32_t per, uint32_t self, uint32_t bw, uint32_t cap,
+                                                     uint32_t* bits, const uint32_t* __restrict__ rank) {
+    const uint32_t n = (uint32_t)d_off[G];            // (the heads of every owner; the tails follow)
+    for (uint32_t i = blockIdx.x * PP_BLK + threadIdx.x; i < n; i += gridDim.x * PP_BLK) {
+        const uint4 h0 = heads[i].q[0];
+        if (!pay_type(h0.z)) continue;
+        const uint32_t o = h0.x / per;
+        if (o == self || o >= G) continue;
+        const uint32_t slot = heads[i].q[1].w;
+        if (slot >= cap) continue;                    // (cap <= 32 bw)
+        const size_t j = (size_t)o * bw + (slot >> 5);
+        const uint32_t b = 1u << (slot & 31u);
+        if (REWRITE) heads[i].q[1].w = rank[j] + (uint32_t)__popc(bits[j] & (b - 1u));
+        else atomicOr(&bits[j], b);
+    }
+}
+
+// cnt2: an RCCL rank's send counts, two words an owner (k_owner_offsets wrote
+// the first)
+__global__ void __launch_bounds__(PR_BLK) k_pay_rank(const uint32_t* __restrict__ bits, uint32_t bw,
+                                                     uint32_t* __restrict__ rank, uint64_t* pcnt, uint64_t* cnt2) {
+    const uint32_t o = blockIdx.x;
+    uint32_t run = 0;
+    for (uint32_t b = 0; b < bw; b += PR_BLK) {       // (uniform: every thread scans)
+        const uint32_t j = b + threadIdx.x;
+        const uint32_t v = j < bw ? (uint32_t)__popc(bits[(size_t)o * bw + j]) : 0u;
+        uint32_t tot;
+        const uint32_t e = block_excl<uint32_t, PR_BLK>(v, &tot);
+        if (j < bw) rank[(size_t)o * bw + j] = run + e;
+        run += tot;
+    }
+    if (threadIdx.x == 0) {
+        pcnt[o] = run;
+        if (cnt2) cnt2[2 * o + 1] = run;
+    }
+}
+
+// lane o: owner o's first row of the payload send buffer (G <= 64)
+__device__ __forceinline__ uint32_t pay_owner_base(const uint64_t* __restrict__ pcnt, uint32_t G) {
+    const uint32_t l = threadIdx.x & 63;
+    const uint32_t c = l < G ? (uint32_t)pcnt[l] : 0u;
+    uint32_t base = c;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(base, d);
+        if (l >= (uint32_t)d) base += y;
+    }
+    return base - c;
+}
+
+// the slot of every row of the payload send buffer, in its order (owner,
+// then rank): a thread per bitmap word stores its set bits' slots from the
+// word's first rank on.  bw is a multiple of 64: a wave's words belong to one
+// owner
+__global__ void __launch_bounds__(PP_BLK) k_pay_list(const uint32_t* __restrict__ bits,
+                                                     const uint32_t* __restrict__ rank, uint32_t G, uint32_t bw,
+                                                     const uint64_t* __restrict__ pcnt, uint32_t* __restrict__ list) {
+    const uint32_t base = pay_owner_base(pcnt, G);    // (every lane, before any return)
+    const uint32_t j = blockIdx.x * PP_BLK + threadIdx.x;
+    const uint32_t o = (j & ~63u) / bw;               // (uniform per wave)
+    const uint32_t ob = __shfl(base, (int)min(o, 63u));
+    if (j >= G * bw) return;
+    uint32_t x = bits[j], r = ob + rank[j];
+    const uint32_t s0 = (j - o * bw) * 32u;
+    for (; x; x &= x - 1) list[r++] = s0 + (uint32_t)__ffs(x) - 1u;
+}
+
+// a wave per row: arena row list[r] to row r of the send buffer, one uint4 a
+// lane (rowlen is a multiple of 4 words; rows and buffers are 16-B aligned)
+__global__ void __launch_bounds__(PP_BLK) k_pay_pack(const uint32_t* __restrict__ list, uint32_t nrows,
+                                                     const uint32_t* __restrict__ rows, uint32_t stride,
+                                                     uint32_t rowlen, uint32_t* __restrict__ out) {
+    const uint32_t l = threadIdx.x & 63;
+    const uint32_t wv = blockIdx.x * (PP_BLK / 64) + (threadIdx.x >> 6), nw = gridDim.x * (PP_BLK / 64);
+    for (uint32_t r = wv; r < nrows; r += nw) {
+        const uint4* src = reinterpret_cast<const uint4*>(rows + (size_t)list[r] * stride);
+        uint4* dst = reinterpret_cast<uint4*>(out + (size_t)r * rowlen);
+        for (uint32_t i = l; i < rowlen / 4; i += 64) dst[i] = src[i];
+    }
 }
 
 // The host boundary (psim_round_emit / psim_get_outbound / psim_round_absorb):
@@ -2232,20 +2358,21 @@ __global__ void k_sh_in(const uint32_t* __restrict__ indeg, const uint8_t* __res
     }
 }
 
-// full strategy: the lowest live id (low: preset to PSIM_NONE), then a wave
-// per node over its member row -- |add & ~remove| and its equality with the
-// lowest live node's; the remove halves are read only once a removal exists
+// full strategy: the lowest live id (low: preset to PSIM_NONE; the flags are
+// replicated, so any shard finds it), then a wave per node over its member
+// row -- |add & ~remove| and its equality with the lowest live node's (ref:
+// that row, wherever it lives); the remove halves are read only once a
+// removal exists
 __global__ void k_sh_low(const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n, uint32_t* low) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && (flags[lo + i] & F_UP)) atomicMin(low, i);
 }
 __global__ void __launch_bounds__(BLK) k_sh_full(const uint32_t* __restrict__ fbits, const uint8_t* __restrict__ flags,
                                                  uint32_t lo, uint32_t n, uint32_t fw, uint32_t tomb,
-                                                 const uint32_t* __restrict__ low, unsigned long long* sf) {
+                                                 const uint32_t* __restrict__ ref, unsigned long long* sf) {
     const uint32_t i = blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);         // (uniform per wave)
     if (i >= n || !(flags[lo + i] & F_UP)) return;
     const uint32_t* row = fbits + (size_t)i * 2 * fw;
-    const uint32_t* ref = fbits + (size_t)*low * 2 * fw;
     uint32_t c = 0;
     bool differs = false;
     for (uint32_t w = lane_id(); w < fw; w += 64) {
@@ -2551,9 +2678,9 @@ struct TmpBuf : DBuf<T> {
 };
 
 enum Kern { KT_EVENTS, KT_PREPARE, KT_CONSUME, KT_SCAN, KT_COMPACT, KT_SORT, KT_EXCHANGE, KT_GATHER,
-            KT_STATS, KT_HOST_EXPORT, KT_HOST_IMPORT, KT_N };
+            KT_STATS, KT_HOST_EXPORT, KT_HOST_IMPORT, KT_PACK, KT_N };
 const char* kKernName[KT_N] = {"events", "prepare", "consume", "scan", "compact", "sort",
-                               "exchange", "gather", "stats", "k_host_export", "k_host_import"};
+                               "exchange", "gather", "stats", "k_host_export", "k_host_import", "pay_pack"};
 
 inline uint32_t grid_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + BLK - 1) / BLK); }
 
@@ -2630,6 +2757,16 @@ struct Shard {
     // pluggable manager
     DBuf<uint32_t> sview, sinv, fbits, pay[2], pay_top;
     int pay_cur = 0;
+    // full, G > 1 (the payload exchange): the (owner, slot) bitmap and its
+    // popcount scan, the per-owner row counts (device, then host), the slot
+    // of every row sent and the rows packed by owner, and the rows other
+    // shards shipped for the next round's
+    // records -- imp_rows of them in source-shard order, fw words each, 2 fw
+    // once tomb_live
+    DBuf<uint32_t> pbits, prank, plist, paysend, pay_imp;
+    DBuf<uint64_t> pcnt_d;
+    std::vector<uint64_t> pcnt;
+    uint32_t pbw = 0, imp_rows = 0;
     DBuf<uint8_t> faulted;              // omission faults: generally omitting nodes (global id)
     DBuf<uint64_t> omit;                // ... sorted send-omission pairs, then receive-omission pairs
     // per destination shard: the send buffer's offsets (2 G + 1: heads of
@@ -2773,6 +2910,10 @@ namespace {
 // grouped by destination in place (phase_route_local); otherwise they go
 // through the owner partition and an exchange
 inline bool local_route(const psim_handle* h) { return h->G == 1 && !h->ranked; }
+
+// a full-strategy handle of more than one shard or rank: STATE and GOSSIP
+// records that cross shards take their ORSet rows along (the payload exchange)
+inline bool ships_rows(const psim_handle* h) { return h->fw != 0 && h->G > 1 && !h->hosted; }
 
 // PSIM_PTL_EARLY, read once: where the early part of k_ptl's list runs (the
 // nodes whose HyParView phase k_relay finished: RoundArgs::n_ptl).  1: as a
@@ -3290,7 +3431,7 @@ int phase_consume(psim_handle* h, Shard* s, RoundArgs& a) {
     if (a.pl && a.strategy == PSIM_STRATEGY_FULL) {
         // snapshots: at most one per node plus one per inbox message
         uint64_t slots = (uint64_t)s->m_in + s->n + 1;
-        if (slots > 0xFFFFFFFFull) return PSIM_ENOMEM;
+        if (slots >= PAY_IMPORT) return PSIM_ENOMEM;  // (word 7's top bit selects the imported rows)
         TRY(s->pay[s->pay_cur].ensure(slots * 2 * h->fw));
         if (h->tomb && !s->tomb_live) {
             // the first round with removes: last round's snapshots were
@@ -3299,8 +3440,24 @@ int phase_consume(psim_handle* h, Shard* s, RoundArgs& a) {
             const size_t rows = in.n / (2 * h->fw);
             if (rows)
                 HIP_TRY(hipMemset2DAsync(in.p + h->fw, 2 * h->fw * 4, 0, h->fw * 4, rows, s->stream));
+            // ... and the imported ones arrived as fw-word rows: spread to
+            // 2 fw words each, the remove halves zero
+            if (s->imp_rows) {
+                DBuf<uint32_t> wide;
+                TRY(wide.ensure((size_t)s->imp_rows * 2 * h->fw));
+                hipError_t e = hipMemsetAsync(wide.p, 0, (size_t)s->imp_rows * 2 * h->fw * 4, s->stream);
+                if (e == hipSuccess)
+                    e = hipMemcpy2DAsync(wide.p, 2 * h->fw * 4, s->pay_imp.p, h->fw * 4, h->fw * 4, s->imp_rows,
+                                         hipMemcpyDeviceToDevice, s->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+                if (e != hipSuccess) { wide.release(); return PSIM_EDEVICE; }
+                s->pay_imp.release();
+                s->pay_imp = wide;
+            }
             s->tomb_live = true;
         }
+        a.pay_imp = s->pay_imp.p;
+        a.imp_stride = s->tomb_live ? 2 * h->fw : h->fw;
         a.pay_out = s->pay[s->pay_cur].p;
         a.pay_in = s->pay[s->pay_cur ^ 1].p;
         a.pay_top = s->pay_top.p;
@@ -3415,7 +3572,8 @@ int route_group(psim_handle* h, Shard* s, bool dense, uint32_t m, bool fixed = f
     const RouteIn in{s->outbox.p, s->okey.p, s->obase.p, s->ocnt.p, dense ? m : n, s->lo,
                      h->cfg.manager == PSIM_MANAGER_PLUGGABLE, dense ? s->recvh.p : nullptr,
                      dense ? s->recvt.p : nullptr, dense && !fixed ? s->wseg.p : nullptr, dense ? h->G : 0u,
-                     fixed ? s->xcap_h : 0u, fixed ? s->xcap_t : 0u, (uint32_t)h->round};
+                     fixed ? s->xcap_h : 0u, fixed ? s->xcap_t : 0u, (uint32_t)h->round,
+                     dense && !fixed && ships_rows(h) ? 1u : 0u, s->idx};
     const uint32_t nsteps = std::max<uint32_t>(1, (in.n_src + RB_STEP - 1) / RB_STEP);
     const uint32_t nblk = std::min<uint32_t>(nsteps, h->rb_blocks);
     const size_t nh = (size_t)nb * nblk;
@@ -3537,6 +3695,32 @@ int phase_route_local(psim_handle* h, Shard* s, bool exact = false) { return rou
 
 void send_counts(Shard* s, uint32_t G);
 
+// the payload exchange's sender side up to the counts (no host wait): mark,
+// rank, and the heads' word 7 rewritten -- after k_owner_part and
+// k_owner_offsets (d_off: the heads' extent).  The arena the round wrote is
+// pay[pay_cur ^ 1] (phase_consume flipped it)
+int pay_mark_rank(psim_handle* h, Shard* s) {
+    const uint32_t G = h->G;
+    const uint64_t cap64 = s->pay[s->pay_cur ^ 1].n / (2 * h->fw);
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(cap64, PAY_IMPORT - 1);
+    s->pbw = payload_bitmap_words(cap);
+    const size_t nbw = (size_t)G * s->pbw;
+    TRY(s->pbits.ensure(nbw));
+    TRY(s->prank.ensure(nbw));
+    TRY(s->pcnt_d.ensure(G));
+    KTimer t(h, s, KT_SORT);                          // (part of the owner partition; KT_PACK is the copy alone)
+    HIP_TRY(hipMemsetAsync(s->pbits.p, 0, nbw * 4, s->stream));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, s->pin[PIN_TOTAL] / PP_BLK + 1);
+    k_pay_mark<false><<<grid, PP_BLK, 0, s->stream>>>(s->sendbuf.p, s->d_off.p, G, h->per, s->idx, s->pbw, cap,
+                                                      s->pbits.p, nullptr);
+    k_pay_rank<<<G, PR_BLK, 0, s->stream>>>(s->pbits.p, s->pbw, s->prank.p, s->pcnt_d.p,
+                                            h->ranked ? h->comm_cnt.p : nullptr);
+    k_pay_mark<true><<<grid, PP_BLK, 0, s->stream>>>(s->sendbuf.p, s->d_off.p, G, h->per, s->idx, s->pbw, cap,
+                                                     s->pbits.p, s->prank.p);
+    HIP_TRY(hipGetLastError());
+    return PSIM_OK;
+}
+
 // G > 1, sender side: the outbox partitioned by owner shard into the send
 // buffer in the wire format (k_owner_part); per-owner counts/offsets on the host
 // fixed: a batched rank round (run_batch_ranked) -- the fixed layout of
@@ -3555,7 +3739,10 @@ int phase_partition(psim_handle* h, Shard* s, bool fixed = false) {
     if (!fixed) TRY(s->sendbuf.ensure(2 * (s->pin[PIN_TOTAL] + 1), 2));   // (the outbox bound bounds the records)
     TRY(s->d_off.ensure(2 * G + 1));
     const bool rccl = h->ranked;
-    if (rccl) TRY(h->comm_cnt.ensure(2 * G + 2));   // (send and receive counts, then 2 words of phase_stats)
+    // (a sharded full handle: a second count word per owner, its payload rows)
+    const bool pay = !fixed && ships_rows(h);
+    const uint32_t cw = pay ? 2u : 1u;
+    if (rccl) TRY(h->comm_cnt.ensure(2 * cw * G + 2));   // (send and receive counts, then 2 words of phase_stats)
     s->soff.assign(2 * G + 1, 0);
     const uint32_t capH = fixed ? s->xcap_h : 0u, capT = fixed ? s->xcap_t : 0u;
     // a batched round's stats: tiles from the count pass, summed into the
@@ -3587,16 +3774,46 @@ int phase_partition(psim_handle* h, Shard* s, bool fixed = false) {
             k_owner_part<true><<<nblk, RB_STEP, 0, s->stream>>>(in, nsteps, spb, G, div, nullptr, s->hoff.p,
                                                                  s->sendbuf.p, nullptr, capH, capT, s->ctl.p, StatsIn{});
         k_owner_offsets<<<1, OO_THREADS, 0, s->stream>>>(s->hoff.p, nblk, G, s->d_off.p, rccl ? h->comm_cnt.p : nullptr,
-                                                  rccl ? s->stat_out.p + STAT_OUT_X : nullptr, capH, capT, s->ctl.p,
+                                                  cw, rccl ? s->stat_out.p + STAT_OUT_X : nullptr, capH, capT, s->ctl.p,
                                                   (uint32_t)h->round, s->idx, s->sendbuf.p, st);
         HIP_TRY(hipGetLastError());
         // an RCCL rank reads the offsets back with the received counts, after
         // the count all-to-all (exchange_rccl): one host wait a round, not two
+        if (!pay) {
+            if (rccl) return PSIM_OK;
+            HIP_TRY(hipMemcpyAsync(s->soff.data(), s->d_off.p, (2 * G + 1) * 8, hipMemcpyDeviceToHost, s->stream));
+            TRY(stream_wait(s));
+        }
+    }
+    if (pay) {                                        // (the same read-backs, with the row counts)
+        TRY(pay_mark_rank(h, s));
         if (rccl) return PSIM_OK;
+        s->pcnt.assign(G, 0);
         HIP_TRY(hipMemcpyAsync(s->soff.data(), s->d_off.p, (2 * G + 1) * 8, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->pcnt.data(), s->pcnt_d.p, G * 8, hipMemcpyDeviceToHost, s->stream));
         TRY(stream_wait(s));
     }
     send_counts(s, G);
+    return PSIM_OK;
+}
+
+// the rows this shard sends (payload_offsets over pcnt) packed by owner into
+// paysend; the counts are on the host (phase_partition's wait, or an RCCL
+// rank's after the count all-to-all)
+int pay_pack(psim_handle* h, Shard* s) {
+    const PayLayout lay = payload_offsets(s->pcnt.data(), h->G, s->tomb_live ? 2 * h->fw : h->fw);
+    if (!lay.rows) return PSIM_OK;
+    if (lay.rows >= PAY_IMPORT) return PSIM_ENOMEM;
+    TRY(s->paysend.ensure(lay.rows * lay.rowlen));
+    TRY(s->plist.ensure(lay.rows));
+    const uint32_t nrows = (uint32_t)lay.rows, words = h->G * s->pbw;
+    k_pay_list<<<(words + PP_BLK - 1) / PP_BLK, PP_BLK, 0, s->stream>>>(s->pbits.p, s->prank.p, h->G, s->pbw,
+                                                                       s->pcnt_d.p, s->plist.p);
+    KTimer t(h, s, KT_PACK);
+    // (rows of 12.5 KB at 10^5 nodes: a wave each, up to 8 blocks of 4 a CU's worth in flight)
+    k_pay_pack<<<std::min<uint32_t>(PP_MAX_BLOCKS, (nrows + PP_BLK / 64 - 1) / (PP_BLK / 64)), PP_BLK, 0,
+                 s->stream>>>(s->plist.p, nrows, s->pay[s->pay_cur ^ 1].p, 2 * h->fw, lay.rowlen, s->paysend.p);
+    HIP_TRY(hipGetLastError());
     return PSIM_OK;
 }
 
@@ -3613,9 +3830,12 @@ void send_counts(Shard* s, uint32_t G) {
 // G > 1, receiver side: heads and tails from the G sources (hc[g] / lc[g]
 // each), already in recvh / recvt in source order; the source table, then
 // the route over the heads
-int phase_receive(psim_handle* h, Shard* s, const std::vector<uint64_t>& hc, const std::vector<uint64_t>& lc) {
+// pbase (a sharded full handle): per source its first imported row
+int phase_receive(psim_handle* h, Shard* s, const std::vector<uint64_t>& hc, const std::vector<uint64_t>& lc,
+                  const std::vector<uint32_t>* pbase = nullptr) {
     const uint32_t G = h->G;
-    s->wseg_host.assign(2 * (G + 1), 0);
+    s->wseg_host.assign((pbase ? 3 : 2) * (G + 1), 0);
+    if (pbase) std::copy(pbase->begin(), pbase->end(), s->wseg_host.begin() + 2 * (G + 1));
     uint64_t m = 0, ml = 0;
     for (uint32_t g = 0; g < G; g++) {
         s->wseg_host[g] = (uint32_t)m;
@@ -3625,7 +3845,7 @@ int phase_receive(psim_handle* h, Shard* s, const std::vector<uint64_t>& hc, con
     }
     s->wseg_host[G] = (uint32_t)m;
     s->wseg_host[2 * G + 1] = (uint32_t)ml;
-    TRY(s->wseg.ensure(2 * (G + 1)));
+    TRY(s->wseg.ensure(s->wseg_host.size()));
     // (the host vector lives until the next round's receive: the copy is
     // ordered on the stream before the route reads it)
     HIP_TRY(hipMemcpyAsync(s->wseg.p, s->wseg_host.data(), s->wseg_host.size() * 4, hipMemcpyHostToDevice,
@@ -3640,17 +3860,32 @@ int phase_receive(psim_handle* h, Shard* s, const std::vector<uint64_t>& hc, con
 // virtual shards of this process: device copies between shard buffers
 int exchange_local(psim_handle* h) {
     const uint32_t G = h->G;
+    const bool pay = ships_rows(h);
+    if (pay) {
+        // every shard's rows packed before any shard copies them
+        for (Shard* s : h->shards) TRY(pay_pack(h, s));
+        for (Shard* s : h->shards) TRY(stream_wait(s));
+    }
     for (Shard* d : h->shards) {
-        std::vector<uint64_t> hc(G), lc(G);
+        std::vector<uint64_t> hc(G), lc(G), pc(G, 0);
         uint64_t m = 0, ml = 0;
         for (Shard* s : h->shards) {
             hc[s->idx] = s->scnt[d->idx];
             lc[s->idx] = s->lcnt[d->idx];
+            if (pay) pc[s->idx] = s->pcnt[d->idx];
             m += hc[s->idx];
             ml += lc[s->idx];
         }
         TRY(d->recvh.ensure(m + 1));
         TRY(d->recvt.ensure(ml + 1));
+        std::vector<uint32_t> pbase;
+        const uint32_t rowlen = d->tomb_live ? 2 * h->fw : h->fw;
+        if (pay) {
+            uint64_t rows = 0;
+            if (!payload_import_bases(pc.data(), G, pbase, &rows)) return PSIM_ENOMEM;
+            TRY(d->pay_imp.ensure(rows * rowlen + 1));
+            d->imp_rows = (uint32_t)rows;
+        }
         {
             KTimer t(h, d, KT_EXCHANGE);
             uint64_t oh = 0, ot = 0;
@@ -3662,15 +3897,21 @@ int exchange_local(psim_handle* h) {
                 if (lc[g])
                     HIP_TRY(hipMemcpyAsync(d->recvt.p + ot, s->sendbuf.p + s->soff[G + d->idx], lc[g] * sizeof(Wire),
                                            hipMemcpyDeviceToDevice, d->stream));
+                if (pay && pc[g]) {                   // (the third region: the rows the heads name)
+                    const PayLayout lay = payload_offsets(s->pcnt.data(), G, rowlen);
+                    HIP_TRY(hipMemcpyAsync(d->pay_imp.p + (size_t)pbase[g] * rowlen,
+                                           s->paysend.p + lay.off[d->idx] * rowlen, pc[g] * rowlen * 4,
+                                           hipMemcpyDeviceToDevice, d->stream));
+                }
                 if (g != d->idx) {
                     h->x_records += hc[g];
-                    h->x_bytes += (hc[g] + lc[g]) * sizeof(Wire);
+                    h->x_bytes += (hc[g] + lc[g]) * sizeof(Wire) + pc[g] * rowlen * 4;
                 }
                 oh += hc[g];
                 ot += lc[g];
             }
         }
-        TRY(phase_receive(h, d, hc, lc));
+        TRY(phase_receive(h, d, hc, lc, pay ? &pbase : nullptr));
     }
     return PSIM_OK;
 }
@@ -3680,21 +3921,40 @@ int exchange_local(psim_handle* h) {
 int exchange_rccl(psim_handle* h) {
     Shard* s = h->shards[0];
     const uint32_t G = h->G;
-    std::vector<uint64_t> hc(G), lc(G);
+    std::vector<uint64_t> hc(G), lc(G), pc(G, 0);
+    const bool pay = ships_rows(h);
+    const uint32_t rowlen = s->tomb_live ? 2 * h->fw : h->fw;
+    std::vector<uint32_t> pbase;
     {
         KTimer t(h, s, KT_EXCHANGE);
         // (k_owner_offsets wrote this rank's counts into comm_cnt[0, G))
-        TRY(h->comm->all_to_all_u64(h->comm_cnt.p, h->comm_cnt.p + G, 1, s->stream));
-        std::vector<uint64_t> rcnt(G);
-        HIP_TRY(hipMemcpyAsync(rcnt.data(), h->comm_cnt.p + G, G * 8, hipMemcpyDeviceToHost, s->stream));
+        // (a sharded full handle: a second word per peer, its payload rows)
+        const uint32_t cw = pay ? 2u : 1u;
+        TRY(h->comm->all_to_all_u64(h->comm_cnt.p, h->comm_cnt.p + cw * G, cw, s->stream));
+        std::vector<uint64_t> rcnt(cw * G);
+        HIP_TRY(hipMemcpyAsync(rcnt.data(), h->comm_cnt.p + cw * G, cw * G * 8, hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipMemcpyAsync(s->soff.data(), s->d_off.p, (2 * G + 1) * 8, hipMemcpyDeviceToHost, s->stream));
+        if (pay) {
+            s->pcnt.assign(G, 0);
+            HIP_TRY(hipMemcpyAsync(s->pcnt.data(), s->pcnt_d.p, G * 8, hipMemcpyDeviceToHost, s->stream));
+        }
         TRY(stream_wait(s));
         send_counts(s, G);
+        PayLayout lay;
+        if (pay) {
+            for (uint32_t g = 0; g < G; g++) pc[g] = rcnt[2 * g + 1];
+            uint64_t rows = 0;
+            if (!payload_import_bases(pc.data(), G, pbase, &rows)) return PSIM_ENOMEM;
+            TRY(s->pay_imp.ensure(rows * rowlen + 1));
+            s->imp_rows = (uint32_t)rows;
+            lay = payload_offsets(s->pcnt.data(), G, rowlen);
+            TRY(pay_pack(h, s));
+        }
         uint64_t m = 0, ml = 0;
         std::vector<uint64_t> roh(G), rot(G);
         for (uint32_t g = 0; g < G; g++) {
-            hc[g] = rcnt[g] & 0xFFFFFFFFull;
-            lc[g] = rcnt[g] >> 32;
+            hc[g] = rcnt[cw * g] & 0xFFFFFFFFull;
+            lc[g] = rcnt[cw * g] >> 32;
             roh[g] = m;
             rot[g] = ml;
             m += hc[g];
@@ -3713,8 +3973,12 @@ int exchange_rccl(psim_handle* h) {
             if (s->lcnt[g]) sends.push_back({(int)g, s->sendbuf.p + s->soff[G + g], s->lcnt[g] * sizeof(Wire)});
             if (hc[g]) recvs.push_back({(int)g, s->recvh.p + roh[g], hc[g] * sizeof(Wire)});
             if (lc[g]) recvs.push_back({(int)g, s->recvt.p + rot[g], lc[g] * sizeof(Wire)});
+            // (the third region; a rank names no rows for itself)
+            if (pay && s->pcnt[g])
+                sends.push_back({(int)g, s->paysend.p + lay.off[g] * rowlen, s->pcnt[g] * rowlen * 4});
+            if (pay && pc[g]) recvs.push_back({(int)g, s->pay_imp.p + (size_t)pbase[g] * rowlen, pc[g] * rowlen * 4});
             h->x_records += s->scnt[g];
-            h->x_bytes += (s->scnt[g] + s->lcnt[g]) * sizeof(Wire);
+            h->x_bytes += (s->scnt[g] + s->lcnt[g]) * sizeof(Wire) + (pay ? s->pcnt[g] * rowlen * 4 : 0);
         }
         TRY(h->comm->exchange(sends, recvs, s->stream));
         if (!self_comm) {
@@ -3727,7 +3991,7 @@ int exchange_rccl(psim_handle* h) {
                                        hipMemcpyDeviceToDevice, s->stream));
         }
     }
-    return phase_receive(h, s, hc, lc);
+    return phase_receive(h, s, hc, lc, pay ? &pbase : nullptr);
 }
 
 // A batched rank round (run_batch_ranked): no host wait.  The counts go
@@ -4565,6 +4829,7 @@ void shard_free(Shard* s) {
     s->cub_tmp.release(); s->ev_ids.release(); s->ev_contacts.release(); s->sendbuf.release(); s->ctl.release();
     s->sview.release(); s->sinv.release(); s->fbits.release(); s->pay[0].release(); s->pay[1].release();
     s->pay_top.release();
+    s->pbits.release(); s->prank.release(); s->plist.release(); s->paysend.release(); s->pay_imp.release(); s->pcnt_d.release();
     if (s->ev_live)
         for (int k = 0; k < Shard::MAXT; k++) {
             (void)hipEventDestroy(s->ev[k][0]);
@@ -4657,7 +4922,9 @@ int psim_create(const psim_config* cfg, psim_handle** out) {
     if (ranked && (local != 1 || !cfg->comm_id || cfg->shard_rank >= world)) return PSIM_EINVAL;
     uint32_t G = hosted ? 3 : ranked ? world : local;
     if (!hosted && (G > 64 || G > cfg->n_nodes)) return PSIM_EINVAL;
-    if (full && G > 1) return PSIM_EUNSUPPORTED;      // gossip payloads are shard-local
+    // (the host boundary's 64-B record cannot carry the ORSet rows a full
+    // handle's STATE and GOSSIP records name; shards and ranks ship them)
+    if (full && hosted) return PSIM_EUNSUPPORTED;
     psim_handle* h = new (std::nothrow) psim_handle();
     if (!h) return PSIM_ENOMEM;
     h->cfg = *cfg;
@@ -5466,22 +5733,55 @@ int psim_get_histograms(psim_handle* h, psim_histograms* out) {
     return PSIM_OK;
 }
 
-// the full strategy's statistics (one shard by construction: psim_create)
+// the full strategy's statistics, over every shard of this process and, on
+// ranks, as a collective (every rank gets the same struct).  The flags are
+// replicated, so every shard finds the lowest live id itself; its row belongs
+// to one shard or rank -- a device pointer serves virtual shards, ranks
+// all-reduce the row (its owner's words, zeros elsewhere: the sum is the row).
+// The ranks' minimum is the maximum of the complement (Comm reduces SUM and MAX)
 static int strategy_hist_full(psim_handle* h, psim_strategy_histograms* out) {
-    Shard* s = h->shards[0];
-    hipStream_t st = s->stream;
+    Shard* s0 = h->shards[0];
+    hipStream_t st = s0->stream;                 // (the caller synchronised every shard's stream)
     TmpBuf<unsigned long long> sf;
-    TmpBuf<uint32_t> low;
+    TmpBuf<uint32_t> low, ref;
     TRY(sf.alloc_on(SF_N, st)); TRY(low.alloc_on(1, st));
     HIP_TRY(hipMemsetAsync(sf.p + SF_MIN, 0xFF, 8, st));
     HIP_TRY(hipMemsetAsync(low.p, 0xFF, 4, st));
-    k_sh_low<<<grid_for(s->n), BLK, 0, st>>>(s->flags.p, s->lo, s->n, low.p);
-    k_sh_full<<<grid_for((uint64_t)s->n * 64), BLK, 0, st>>>(s->fbits.p, s->flags.p, s->lo, s->n, h->fw,
-                                                           h->tomb ? 1u : 0u, low.p, sf.p);
+    k_sh_low<<<grid_for(h->N), BLK, 0, st>>>(s0->flags.p, 0, h->N, low.p);
     HIP_TRY(hipGetLastError());
+    uint32_t lowest = PSIM_NONE;
+    HIP_TRY(hipMemcpyAsync(&lowest, low.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (lowest != PSIM_NONE) {
+        Shard* o = owner_of(h, lowest);
+        const uint32_t* rp = o ? o->fbits.p + (size_t)(lowest - o->lo) * 2 * h->fw : nullptr;
+        if (h->ranked && h->world > 1) {
+            TRY(ref.alloc_on(2 * h->fw, st));
+            if (rp) HIP_TRY(hipMemcpyAsync(ref.p, rp, 2 * h->fw * 4, hipMemcpyDeviceToDevice, st));
+            TRY(h->comm->all_reduce(ref.p, 2 * h->fw, CType::U32, COp::SUM, st));
+            rp = ref.p;
+        }
+        if (!rp) return PSIM_ESTATE;
+        for (Shard* s : h->shards)
+            if (s->n)
+                k_sh_full<<<grid_for((uint64_t)s->n * 64), BLK, 0, st>>>(s->fbits.p, s->flags.p, s->lo, s->n, h->fw,
+                                                                       h->tomb ? 1u : 0u, rp, sf.p);
+        HIP_TRY(hipGetLastError());
+    }
     unsigned long long v[SF_N];
     HIP_TRY(hipMemcpyAsync(v, sf.p, sizeof v, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (h->ranked && h->world > 1) {
+        // (a rank without live nodes: SF_MIN is still all ones, its complement 0)
+        uint64_t w[SF_N] = {v[SF_NUP], v[SF_SUM], v[SF_AGREE], v[SF_MAX], ~(uint64_t)v[SF_MIN]};
+        TRY(h->comm_cnt.ensure(SF_N));
+        HIP_TRY(hipMemcpyAsync(h->comm_cnt.p, w, sizeof w, hipMemcpyHostToDevice, st));
+        TRY(h->comm->all_reduce(h->comm_cnt.p, 3, CType::U64, COp::SUM, st));
+        TRY(h->comm->all_reduce(h->comm_cnt.p + 3, 2, CType::U64, COp::MAX, st));
+        HIP_TRY(hipMemcpyAsync(w, h->comm_cnt.p, sizeof w, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        v[SF_NUP] = w[0]; v[SF_SUM] = w[1]; v[SF_AGREE] = w[2]; v[SF_MAX] = w[3]; v[SF_MIN] = ~w[4];
+    }
     out->n_up = v[SF_NUP];
     if (v[SF_NUP]) {
         out->members_min = v[SF_MIN]; out->members_max = v[SF_MAX]; out->members_sum = v[SF_SUM];
@@ -5726,6 +6026,9 @@ static std::vector<Section> snap_sections(psim_handle* h, Shard* s, const ShardH
         if (s->sinv.p) v.push_back({s->sinv.p, n * PSIM_SVIEW_CAP * 4});
         if (s->fbits.p) v.push_back({s->fbits.p, n * 2 * h->fw * 4});
         if (sh.pay_rows) v.push_back({s->pay[sh.pay_cur ^ 1].p, (size_t)sh.pay_rows * 2 * h->fw * 4});
+        // (a sharded full handle: the in-flight rows other shards shipped --
+        // pad2[0] of them, fw words each, 2 fw once pad[0] says removes exist)
+        if (sh.pad2[0]) v.push_back({s->pay_imp.p, (size_t)sh.pad2[0] * (sh.pad[0] ? 2 : 1) * h->fw * 4});
     }
     return v;
 }
@@ -5747,6 +6050,7 @@ int psim_snapshot(psim_handle* h, void* buf, size_t cap, size_t* need) {
         sh.pad[0] = s->tomb_live ? 1u : 0u;            // full: snapshots carry remove rows
         sh.pad[1] = s->mapx.p ? std::min<uint32_t>(read1(s, s->mapx_top.p), (uint32_t)(s->mapx.n / IDMAP_EXT)) : 0u;
         sh.out_rows = s->outx.p ? std::min<uint32_t>(read1(s, s->outx_top.p), (uint32_t)(s->outx.n / OUT_EXT)) : 0u;
+        sh.pad2[0] = s->imp_rows;
         heads.push_back(sh);
         total += sizeof(ShardHead);
         for (const Section& x : snap_sections(h, s, sh)) total += x.bytes;
@@ -5797,6 +6101,7 @@ int psim_restore(psim_handle* h, const void* buf, size_t size) {
             if (sh.lo != s->lo || sh.n != s->n || sh.pay_cur > 1) return PSIM_EINVAL;
             if ((size_t)sh.pad[1] * IDMAP_EXT > s->mapx.n) return PSIM_EINVAL;
             if (sh.out_rows && !s->outx.p) return PSIM_EINVAL;
+            if (sh.pad2[0] && !ships_rows(h)) return PSIM_EINVAL;
             for (const Section& x : snap_sections(h, s, sh)) {
                 if ((size_t)(end - q) < x.bytes) return PSIM_EINVAL;
                 q += x.bytes;
@@ -5819,6 +6124,8 @@ int psim_restore(psim_handle* h, const void* buf, size_t size) {
         if (s->tomb_live) h->tomb = true;
         TRY(s->inbox.ensure((size_t)sh.m_in + 1));
         if (sh.pay_rows) TRY(s->pay[s->pay_cur ^ 1].ensure((size_t)sh.pay_rows * 2 * h->fw));
+        if (sh.pad2[0]) TRY(s->pay_imp.ensure((size_t)sh.pad2[0] * 2 * h->fw));
+        s->imp_rows = sh.pad2[0];
         if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE && s->pay_top.p)
             HIP_TRY(hipMemcpy(s->pay_top.p, &sh.pay_rows, 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(s->mapx_top.p, &sh.pad[1], 4, hipMemcpyHostToDevice));

@@ -153,7 +153,15 @@ struct RoundArgs {
     uint32_t faults, n_omit_s, n_omit_r;
     const uint8_t* faulted;
     const uint64_t* omit;
+    // full, more than one shard or rank: the snapshot rows other shards
+    // shipped with last round's records (psim_engine.hip, the payload
+    // exchange), imp_stride words apart (fw, or 2 fw once removes exist); a
+    // record whose word 7 has PAY_IMPORT set names row (word 7 & ~PAY_IMPORT)
+    // of pay_imp instead of a slot of pay_in
+    const uint32_t* pay_imp;
+    uint32_t imp_stride;
 };
+constexpr uint32_t PAY_IMPORT = 0x80000000u;
 
 __global__ void k_consume(RoundArgs args);
 // lane-per-node SHUFFLE relays ahead of k_consume (psim_consume.hip)
@@ -298,7 +306,7 @@ constexpr uint32_t layout_sig() {
         offsetof(RoundArgs, hdr), offsetof(RoundArgs, conn), offsetof(RoundArgs, outx_rows),
         offsetof(RoundArgs, desc), offsetof(RoundArgs, desc_lite), offsetof(RoundArgs, stat_ptle), offsetof(RoundArgs, stat_pt),
         offsetof(RoundArgs, rec_out), offsetof(RoundArgs, okey), offsetof(RoundArgs, ktime),
-        offsetof(RoundArgs, ctl), offsetof(RoundArgs, fbits), offsetof(RoundArgs, omit),
+        offsetof(RoundArgs, ctl), offsetof(RoundArgs, fbits), offsetof(RoundArgs, omit), offsetof(RoundArgs, pay_imp),
         sizeof(Hdr), sizeof(Msg), sizeof(upart_t), PSIM_SHORT_TAIL, PTL_BLOCK, KEY_DST_BITS, KEY_BCAST,
         PSIM_ACTIVE_CAP, PSIM_PASSIVE_CAP, PSIM_EXCHANGE_CAP, PSIM_PT_ROOTS, PSIM_PT_OUT_CAP, PSIM_IDMAP_CAP,
         PSIM_CONN_CAP, PSIM_SVIEW_CAP, OUT_IN, IDMAP_IN, RT_SET, RT_WORDS, NST, CRASH_GRAIN_SHIFT};

@@ -373,6 +373,13 @@ DEV uint32_t full_nth(const Pw& w, uint32_t k) {
     return NONE;
 }
 
+// the ORSet rows a STATE or GOSSIP record names in its word 7: a slot of this
+// shard's arena, or (PAY_IMPORT) a row another shard shipped with the record
+DEV const uint32_t* pay_row(uint32_t slot) {
+    if (slot & PAY_IMPORT) return kargs().pay_imp + (size_t)(slot & ~PAY_IMPORT) * kargs().imp_stride;
+    return kargs().pay_in + (size_t)slot * 2 * kargs().fw;
+}
+
 // a snapshot of the state for the messages of one gossip: one arena slot per
 // distinct state the node sends this round
 DEV uint32_t full_snapshot(Pw& w) {
@@ -525,7 +532,7 @@ DEV void pl_handle(Pw& w, uint32_t type, uint32_t src, uint32_t a0, uint32_t slo
         if (w.h.join_contact != src) break;
         w.h.join_contact = NONE;
         if (full) {                // join/3 full:49-55
-            full_merge(w, kargs().pay_in + (size_t)slot * 2 * kargs().fw);
+            full_merge(w, pay_row(slot));
             if (kargs().fanout) w.gossip_due = true;
             else full_gossip(w);
         } else {
@@ -534,7 +541,7 @@ DEV void pl_handle(Pw& w, uint32_t type, uint32_t src, uint32_t a0, uint32_t slo
         break;
     case PSIM_PL_GOSSIP:           // handle_message/2 full:99-116
         if (!full) break;
-        if (!full_merge(w, kargs().pay_in + (size_t)slot * 2 * kargs().fw)) {
+        if (!full_merge(w, pay_row(slot))) {
             // a merged removal of ourselves: the manager stops (pl:1182-1188)
             // before the gossip it cast goes out
             if (kargs().tomb && ((w.row[kargs().fw + (w.me >> 5)] >> (w.me & 31u)) & 1u)) { w.stop = true; break; }
