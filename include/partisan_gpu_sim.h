@@ -397,6 +397,61 @@ typedef struct psim_graph_metrics {
     uint64_t reserved[8];
 } psim_graph_metrics;
 
+/* The broadcast tree of one Plumtree root R, computed on the device
+ * (DESIGN.md "Broadcast tree"): what partisan_plumtree_broadcast:
+ * debug_get_tree/2 (pt:235-243) folds out of debug_get_peers/2 (pt:222-231,
+ * all_peers/3 pt:627-631) over every node.  Everything is an integer, so the
+ * struct is bit-exact whatever the order of any sum.
+ *   Sets of a live node i for R: the first root slot k with
+ *     pt_root[k] == (R | PSIM_MAP_BIT) gives its eager and lazy runs; a node
+ *     without such a slot answers (common_eagers, []).
+ *   An entry e names node p = e & ~PSIM_MAP_BIT.  p is live if p < n_nodes
+ *     and node p is up.
+ *   E_i: the distinct p over i's eager entries with p != i and p live; Z_i the
+ *     same over its lazy entries.  T: the ordered pairs (i, p), p in E_i.
+ *   Liveness is the only filter: partitions are ignored, as in
+ *     psim_histograms.  Bins as there: bin k = value k, the last bin =
+ *     PSIM_HIST_BINS - 1 or more.
+ *   The two BFS passes start at R and run levels d = 1, 2, ... while
+ *     d <= the level cap; a level that finds no node ends the pass.  L is the
+ *     link set psim_graph_metrics counts: active view, p != i, p live, repeats
+ *     dropped.  With R not live every field from `depth` on is zero. */
+typedef struct psim_tree_metrics {
+    uint64_t n_up;                           /* live nodes */
+    uint64_t root_live;                      /* 1: R is live */
+    uint64_t slot_nodes;                     /* live nodes that hold a slot for R */
+    uint64_t eager_entries, lazy_entries;    /* raw entries of the live nodes' sets for R */
+    uint64_t eager_links;                    /* |T| = sum of |E_i| */
+    uint64_t lazy_links;                     /* sum of |Z_i| */
+    uint64_t both_links;                     /* sum of |E_i & Z_i| */
+    uint64_t eager_both_forms;               /* (i, p) in T whose eager entries hold both p and p | PSIM_MAP_BIT */
+    uint64_t self_entries;                   /* entries, eager or lazy, that decode to i itself */
+    uint64_t eager_dead, lazy_dead;          /* entries that decode to another node that is not live */
+    uint64_t eager_nonmember;                /* (i, p) in T with p not in i's active view */
+    uint64_t lazy_nonmember;                 /* p in Z_i not in i's active view */
+    uint64_t eager_symmetric;                /* (i, p) in T with (p, i) in T */
+    uint64_t eager_out[PSIM_HIST_BINS];      /* live nodes by |E_i| */
+    uint64_t lazy_out[PSIM_HIST_BINS];       /* live nodes by |Z_i| */
+    uint64_t eager_in[PSIM_HIST_BINS];       /* live nodes by in-degree in T */
+    uint64_t depth[PSIM_HIST_BINS];          /* BFS over T: nodes v != R by finite depth; bin 0: 0 */
+    uint64_t depth_sum;                      /* the exact sum of those depths (not saturated) */
+    uint64_t depth_max;                      /* the largest finite depth */
+    uint64_t reached;                        /* their number */
+    uint64_t unreached;                      /* root_live (n_up - 1) - reached: the nodes a broadcast
+                                                reaches only through graft */
+    uint64_t links_from_reached;             /* sum of |E_i| over i at finite depth, R included: the
+                                                payload copies of a broadcast over frozen sets */
+    uint64_t levels;                         /* levels the BFS over T ran (the last one may have found nothing) */
+    uint64_t truncated;                      /* 1: the level cap ended either BFS with level `cap` still
+                                                finding a node; nodes farther away count as unreached */
+    uint64_t overlay_reached;                /* BFS over L: nodes v != R at finite distance */
+    uint64_t both_reached;                   /* v != R finite in both */
+    uint64_t depth_sum_both, dist_sum_both;  /* over those: tree depths, overlay distances (the stretch) */
+    uint64_t deeper;                         /* ... whose tree depth exceeds the overlay distance */
+    uint64_t shallower;                      /* ... the opposite (eager links to non-members exist) */
+    uint64_t reserved[8];
+} psim_tree_metrics;
+
 typedef struct psim_handle psim_handle;
 
 void psim_default_config(psim_config *cfg);
@@ -552,6 +607,17 @@ int psim_get_strategy_histograms(psim_handle *h, psim_strategy_histograms *out);
  * same struct). */
 int psim_get_graph_metrics(psim_handle *h, const uint32_t *sources, size_t n_sources, uint32_t max_levels,
                            psim_graph_metrics *out);
+/* The broadcast tree of Plumtree root `root` (psim_tree_metrics above), on
+ * the device, for HyParView and X-BOT handles with cfg.plumtree set, of any
+ * shard count.  max_levels caps both BFS passes: 0 means
+ * PSIM_GRAPH_MAX_LEVELS, and larger values are clamped to it.  PSIM_EINVAL
+ * for a null h or out; PSIM_EUNSUPPORTED for pluggable handles, host-exchange
+ * handles and plumtree = 0; PSIM_ERANGE for root >= n_nodes (a dead root is
+ * legal: the BFS fields stay zero); PSIM_ESTATE with a round open.
+ * Read-only: the rounds stepped after it are those of a run without it.  A
+ * collective on rank handles (every rank calls with the same arguments; every
+ * rank gets the same struct).  No Erlang binding yet. */
+int psim_get_tree_metrics(psim_handle *h, uint32_t root, uint32_t max_levels, psim_tree_metrics *out);
 /* Snapshot of the whole simulation state of this process (node rows,
  * in-flight messages, round, events not yet applied are not included):
  * with buf == NULL (or cap too small) only *need is set.  psim_restore

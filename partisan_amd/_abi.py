@@ -153,6 +153,27 @@ class PsimGraphMetrics(C.Structure):
     ]
 
 
+class PsimTreeMetrics(C.Structure):
+    _fields_ = [
+        ("n_up", C.c_uint64), ("root_live", C.c_uint64), ("slot_nodes", C.c_uint64),
+        ("eager_entries", C.c_uint64), ("lazy_entries", C.c_uint64),
+        ("eager_links", C.c_uint64), ("lazy_links", C.c_uint64), ("both_links", C.c_uint64),
+        ("eager_both_forms", C.c_uint64), ("self_entries", C.c_uint64),
+        ("eager_dead", C.c_uint64), ("lazy_dead", C.c_uint64),
+        ("eager_nonmember", C.c_uint64), ("lazy_nonmember", C.c_uint64),
+        ("eager_symmetric", C.c_uint64),
+        ("eager_out", C.c_uint64 * HIST_BINS), ("lazy_out", C.c_uint64 * HIST_BINS),
+        ("eager_in", C.c_uint64 * HIST_BINS),
+        ("depth", C.c_uint64 * HIST_BINS), ("depth_sum", C.c_uint64), ("depth_max", C.c_uint64),
+        ("reached", C.c_uint64), ("unreached", C.c_uint64), ("links_from_reached", C.c_uint64),
+        ("levels", C.c_uint64), ("truncated", C.c_uint64),
+        ("overlay_reached", C.c_uint64), ("both_reached", C.c_uint64),
+        ("depth_sum_both", C.c_uint64), ("dist_sum_both", C.c_uint64),
+        ("deeper", C.c_uint64), ("shallower", C.c_uint64),
+        ("reserved", C.c_uint64 * 8),
+    ]
+
+
 NODE_VIEW_DTYPE = np.dtype(PsimNodeView)
 STRATEGY_VIEW_DTYPE = np.dtype(PsimStrategyView)
 STATS_DTYPE = np.dtype(PsimRoundStats)
@@ -203,6 +224,7 @@ GPU_ONLY = {
     # (no oracle twin: the tests' reference is numpy over the oracle's views)
     "get_strategy_histograms": (C.c_int, [_H, C.POINTER(PsimStrategyHistograms)]),
     "get_graph_metrics": (C.c_int, [_H, _P32, C.c_size_t, C.c_uint32, C.POINTER(PsimGraphMetrics)]),
+    "get_tree_metrics": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(PsimTreeMetrics)]),
 }
 # the host boundary (host-exchange handles: sim.HostSim, wire.check)
 HOST_BOUNDARY = {

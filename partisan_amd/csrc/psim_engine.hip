@@ -2593,6 +2593,261 @@ __global__ void __launch_bounds__(BLK) k_gm_level(uint32_t n, unsigned long long
     if (threadIdx.x == 0) { atomicOr(&lv[0], sh_lv[0]); atomicAdd(&lv[1], sh_lv[1]); }
 }
 
+// ------------------------------------------------------ broadcast tree --
+// psim_get_tree_metrics: root R's eager / lazy sets of every live node
+// (psim_tree_metrics in the header defines every field).
+//   k_tm_rows (count)  LN lanes a node; finds R's slot in the root row, holds
+//                      the eager and the lazy run RT_SET / LN entries a lane,
+//                      decodes, drops self, tests liveness, marks the first
+//                      occurrence of a peer over both identity forms by a
+//                      compare against every lane of the group, tests the
+//                      active view, counts the entry-level fields and writes
+//                      |E_i| (a byte, by global id)
+//   scan_excl          the counts (all-gathered across ranks) -> row offsets
+//   k_tm_rows (pack)   the same group writes E_i at its offset and adds the
+//                      in-degrees
+//   k_tm_sym           (i, p) in T: is i in p's row?
+//   k_tm_bfs           one level of a single-source BFS over CSR or
+//                      HyParView rows, depths in an N-word array
+//   k_tm_final         the in-degree histogram and the two depth arrays
+// tm layout (summed over ranks): two histograms, then scalars
+enum { TM_EOUT = 0, TM_LOUT = 1, TM_NUP = 2 * PSIM_HIST_BINS, TM_SLOT, TM_EENT, TM_LENT, TM_ELINKS, TM_LLINKS,
+       TM_BOTH, TM_FORMS, TM_SELF, TM_EDEAD, TM_LDEAD, TM_ENM, TM_LNM, TM_N };
+constexpr uint32_t TM_SCALARS = TM_N - TM_NUP;
+// tf layout (over the whole CSR, the same on every rank): the in-degree histogram, then scalars
+enum { TF_LFR = PSIM_HIST_BINS, TF_OREACH, TF_BOTH, TF_DSUM, TF_LSUM, TF_DEEPER, TF_SHALLOWER, TF_N };
+
+// a run of at most RT_SET entries held by a group of LN lanes: entry
+// c * LN + g in e[c] of the group's lane g
+template <uint32_t LN>
+struct TmRun {
+    static constexpr uint32_t C = RT_SET / LN;
+    uint32_t e[C], p[C];
+    bool keep[C];                         // the entry names a live node other than the owner
+    uint32_t n;
+};
+
+// loads the run; counts the lane's entries that name the owner / a dead node
+template <uint32_t LN>
+DEV void tm_load(TmRun<LN>& r, const uint32_t* __restrict__ src, uint32_t n, uint32_t me,
+                 const uint8_t* __restrict__ flags, uint32_t N, uint32_t& self, uint32_t& dead) {
+    const uint32_t g = lane_id() % LN;
+    r.n = n;
+#pragma unroll
+    for (uint32_t c = 0; c < TmRun<LN>::C; c++) {
+        const bool v = c * LN + g < n;
+        r.e[c] = v ? src[c * LN + g] : PSIM_NONE;
+        r.p[c] = r.e[c] & ~PSIM_MAP_BIT;
+        const bool own = v && r.p[c] == me, live = v && sh_live(flags, N, r.p[c]);
+        r.keep[c] = live && !own;
+        self += own ? 1u : 0u;
+        dead += v && !own && !live ? 1u : 0u;
+    }
+}
+
+// every entry of run b, in order, against the lane's entries of run a:
+// dup[c]: an entry of b before position c * LN + g names the same node (a == b:
+// the entry is no first occurrence); hit[c]: some entry of b names it;
+// atom[c] / map[c]: b holds the node's plain / PSIM_MAP_BIT form.  The loop
+// bounds are the same in all lanes of a group, and a lane reads its own group only
+template <uint32_t LN>
+DEV void tm_match(const TmRun<LN>& a, const TmRun<LN>& b, bool* dup, bool* hit, bool* atom, bool* map) {
+    constexpr uint32_t C = TmRun<LN>::C;
+    const uint32_t l = lane_id(), g = l % LN, gb = l - g;
+#pragma unroll
+    for (uint32_t c = 0; c < C; c++) dup[c] = hit[c] = atom[c] = map[c] = false;
+#pragma unroll
+    for (uint32_t c2 = 0; c2 < C; c2++)
+        for (uint32_t y = 0; y < LN && c2 * LN + y < b.n; y++) {
+            const uint32_t ev = shfl(b.e[c2], (int)(gb + y)), pv = ev & ~PSIM_MAP_BIT;
+#pragma unroll
+            for (uint32_t c = 0; c < C; c++) {
+                const bool same = pv == a.p[c];
+                dup[c] |= same && c2 * LN + y < c * LN + g;
+                hit[c] |= same;
+                atom[c] |= ev == a.p[c];
+                map[c] |= ev == (a.p[c] | PSIM_MAP_BIT);
+            }
+        }
+}
+
+// off == nullptr: the count pass (statistics into tm, |E_i| into
+// cnt[lo + i]); else the pack pass (E_i into adj at off[lo + i], indeg)
+template <uint32_t LN>
+__global__ void __launch_bounds__(BLK) k_tm_rows(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ act,
+                                                 const uint32_t* __restrict__ pt_rt,
+                                                 const uint32_t* __restrict__ pt_eag,
+                                                 const uint32_t* __restrict__ pt_laz,
+                                                 const uint32_t* __restrict__ pt_com,
+                                                 const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n,
+                                                 uint32_t N, uint32_t root, uint8_t* cnt,
+                                                 const uint32_t* __restrict__ off, uint32_t* adj, uint32_t* indeg,
+                                                 unsigned long long* tm) {
+    static_assert(LN == 16 || LN == 64, "a DPP row or a wave a node");
+    static_assert(PSIM_PT_ROOTS == 4 && RT_SET == 64, "the counts of a pool: one byte a slot, 64 entries");
+    constexpr uint32_t C = TmRun<LN>::C;
+    constexpr uint64_t GROUP = LN == 64 ? ~0ull : (1ull << (LN % 64)) - 1ull;     // a group's lanes of a ballot
+    __shared__ unsigned long long sh[TM_N];
+    for (uint32_t j = threadIdx.x; j < TM_N; j += blockDim.x) sh[j] = 0;
+    __syncthreads();
+    const uint32_t l = lane_id(), g = l % LN, gb = l - g;
+    const uint32_t i = (blockIdx.x * BLK + threadIdx.x) / LN, me = lo + i;
+    const bool up = i < n && (flags[me] & F_UP);
+    uint32_t s[TM_SCALARS] = {0};                     // the lane's share of the scalars
+    if (up) {                                         // (the same in all lanes of a group)
+        // R's slot, or the common set
+        const uint32_t* rt = pt_rt + (size_t)i * RT_WORDS;
+        int k = -1;
+        for (int q = PSIM_PT_ROOTS - 1; q >= 0; q--) k = rt[q] == (root | PSIM_MAP_BIT) ? q : k;
+        uint32_t en, ln = 0, eo = 0, zo = 0;
+        if (k >= 0) {
+            const uint32_t ce = rt[RT_EN], cl = rt[RT_LN];
+            for (int q = 0; q < k; q++) { eo += (ce >> (8 * q)) & 0xFFu; zo += (cl >> (8 * q)) & 0xFFu; }
+            eo = min(eo, RT_SET); zo = min(zo, RT_SET);
+            en = min((ce >> (8 * k)) & 0xFFu, RT_SET - eo);
+            ln = min((cl >> (8 * k)) & 0xFFu, RT_SET - zo);
+        } else {
+            en = min((uint32_t)hdr[i].com_n, (uint32_t)PSIM_PT_MEMBERS_CAP);
+        }
+        const uint32_t* er = k >= 0 ? pt_eag + (size_t)i * RT_SET + eo : pt_com + (size_t)i * PSIM_PT_MEMBERS_CAP;
+        TmRun<LN> E;
+        bool dup[C], hit[C], atom[C], map[C];
+        tm_load(E, er, en, me, flags, N, s[TM_SELF - TM_NUP], s[TM_EDEAD - TM_NUP]);
+        tm_match(E, E, dup, hit, atom, map);
+        // E_i: the first occurrences among the kept entries, packed in entry order
+        uint32_t ne = 0;
+        bool first[C];
+#pragma unroll
+        for (uint32_t c = 0; c < C; c++) {
+            first[c] = E.keep[c] && !dup[c];
+            const uint64_t b = (ballot(first[c]) >> gb) & GROUP;
+            if (off && first[c]) {
+                adj[off[me] + ne + popc(b & ((1ull << g) - 1ull))] = E.p[c];
+                atomicAdd(&indeg[E.p[c]], 1u);
+            }
+            ne += popc(b);
+        }
+        if (!off) {
+            const uint32_t an = min((uint32_t)hdr[i].act_n, (uint32_t)PSIM_ACTIVE_CAP);
+            uint32_t av[PSIM_ACTIVE_CAP];
+#pragma unroll
+            for (uint32_t q = 0; q < PSIM_ACTIVE_CAP; q++) av[q] = q < an ? act[(size_t)i * PSIM_ACTIVE_CAP + q] : PSIM_NONE;
+#pragma unroll
+            for (uint32_t c = 0; c < C; c++) {
+                if (!first[c]) continue;
+                bool mem = false;
+#pragma unroll
+                for (uint32_t q = 0; q < PSIM_ACTIVE_CAP; q++) mem |= av[q] == E.p[c];
+                s[TM_ENM - TM_NUP] += mem ? 0u : 1u;
+                s[TM_FORMS - TM_NUP] += atom[c] && map[c] ? 1u : 0u;
+            }
+            uint32_t nz = 0;
+            if (ln) {                                 // (the same in all lanes of a group)
+                TmRun<LN> Z;
+                bool zdup[C], inE[C];
+                tm_load(Z, pt_laz + (size_t)i * RT_SET + zo, ln, me, flags, N, s[TM_SELF - TM_NUP],
+                        s[TM_LDEAD - TM_NUP]);
+                tm_match(Z, Z, zdup, hit, atom, map);
+                tm_match(Z, E, dup, inE, atom, map);
+#pragma unroll
+                for (uint32_t c = 0; c < C; c++) {
+                    if (!Z.keep[c] || zdup[c]) continue;
+                    bool mem = false;
+#pragma unroll
+                    for (uint32_t q = 0; q < PSIM_ACTIVE_CAP; q++) mem |= av[q] == Z.p[c];
+                    nz++;
+                    s[TM_LNM - TM_NUP] += mem ? 0u : 1u;
+                    s[TM_BOTH - TM_NUP] += inE[c] ? 1u : 0u;
+                }
+                s[TM_LLINKS - TM_NUP] += nz;
+                for (int d = LN / 2; d; d >>= 1) nz += (uint32_t)__shfl_xor((int)nz, d);
+            }
+            if (g == 0) {
+                cnt[me] = (uint8_t)ne;
+                s[TM_NUP - TM_NUP] = 1; s[TM_SLOT - TM_NUP] = k >= 0 ? 1u : 0u;
+                s[TM_EENT - TM_NUP] = en; s[TM_LENT - TM_NUP] = ln; s[TM_ELINKS - TM_NUP] = ne;
+                atomicAdd(&sh[TM_EOUT * PSIM_HIST_BINS + hbin(ne)], 1ull);
+                atomicAdd(&sh[TM_LOUT * PSIM_HIST_BINS + hbin(nz)], 1ull);
+            }
+        }
+    }
+    if (off) return;
+#pragma unroll
+    for (uint32_t j = 0; j < TM_SCALARS; j++) {
+        const uint32_t v = sh_wave_sum(s[j]);
+        if (l == 0 && v) atomicAdd(&sh[TM_NUP + j], (unsigned long long)v);
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < TM_N; j += blockDim.x)
+        if (sh[j]) atomicAdd(&tm[j], sh[j]);
+}
+
+// the links of T whose reverse is a link of T (every process over the whole CSR)
+__global__ void k_tm_sym(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
+                         const uint32_t* __restrict__ adj, uint32_t n, unsigned long long* sym) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t c = 0;
+    if (i < n) {
+        const uint32_t* row = adj + off[i];
+        for (uint32_t k = 0, ci = cnt[i]; k < ci; k++) c += sh_has(off, cnt, adj, row[k], i) ? 1u : 0u;
+    }
+    c = sh_wave_sum(c);
+    if (lane_id() == 0 && c) atomicAdd(sym, (unsigned long long)c);
+}
+
+// level d of a single-source BFS (rows as k_gm_push reads them): a node at
+// depth d - 1 claims each out-neighbour that has no depth yet; found: the
+// nodes claimed
+__global__ void k_tm_bfs(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
+                         const uint32_t* __restrict__ adj, uint32_t n, uint32_t d, uint32_t* depth,
+                         unsigned long long* found) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t c = 0;
+    if (i < n && depth[i] == d - 1) {
+        const uint32_t* row = adj + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP);
+        for (uint32_t k = 0, ci = cnt[i]; k < ci; k++) {
+            const uint32_t p = row[k];
+            if (p < n && depth[p] == PSIM_NONE && atomicCAS(&depth[p], PSIM_NONE, d) == PSIM_NONE) c++;
+        }
+    }
+    c = sh_wave_sum(c);
+    if (lane_id() == 0 && c) atomicAdd(found, (unsigned long long)c);
+}
+
+// per live node: its in-degree in T; dt / dl (nullptr: R is not live): its
+// depth over T and its distance over L (PSIM_NONE: none)
+__global__ void __launch_bounds__(BLK) k_tm_final(const uint32_t* __restrict__ indeg,
+                                                  const uint8_t* __restrict__ cnt,
+                                                  const uint8_t* __restrict__ flags, uint32_t n, uint32_t root,
+                                                  const uint32_t* __restrict__ dt,
+                                                  const uint32_t* __restrict__ dl, unsigned long long* tf) {
+    __shared__ unsigned long long sh[TF_N];
+    for (uint32_t j = threadIdx.x; j < TF_N; j += blockDim.x) sh[j] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t s[TF_N - TF_LFR] = {0};
+    if (i < n && (flags[i] & F_UP)) {
+        atomicAdd(&sh[hbin(indeg[i])], 1ull);
+        const uint32_t a = dt ? dt[i] : PSIM_NONE, b = dl ? dl[i] : PSIM_NONE;
+        if (a != PSIM_NONE) s[TF_LFR - TF_LFR] = cnt[i];
+        if (i != root) {
+            if (b != PSIM_NONE) s[TF_OREACH - TF_LFR] = 1;
+            if (a != PSIM_NONE && b != PSIM_NONE) {
+                s[TF_BOTH - TF_LFR] = 1; s[TF_DSUM - TF_LFR] = a; s[TF_LSUM - TF_LFR] = b;
+                s[TF_DEEPER - TF_LFR] = a > b ? 1u : 0u; s[TF_SHALLOWER - TF_LFR] = a < b ? 1u : 0u;
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < TF_N - TF_LFR; j++) {
+        const uint32_t v = sh_wave_sum(s[j]);         // (a wave's depths: 64 * 4096 at the most)
+        if (lane_id() == 0 && v) atomicAdd(&sh[TF_LFR + j], (unsigned long long)v);
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < TF_N; j += blockDim.x)
+        if (sh[j]) atomicAdd(&tf[j], sh[j]);
+}
+
 // ------------------------------------------------------------- buffers --
 template <typename T>
 struct DBuf {
@@ -5798,45 +6053,61 @@ struct ShCsr {
     TmpBuf<uint32_t> off, base, adj;
     TmpBuf<unsigned long long> tot;
 };
+// the counts and offsets of a CSR, zeroed, before its count pass
+static int csr_alloc(psim_handle* h, hipStream_t st, ShCsr& c) {
+    const size_t npad = (size_t)h->per * h->G;
+    TRY(c.tot.alloc_on(1, st));
+    TRY(c.cnt.alloc_on(npad + 1, st)); TRY(c.off.alloc_on(npad + 1, st));
+    TRY(c.base.alloc_on(h->ranked ? (uint32_t)h->world : 1u, st));
+    return PSIM_OK;
+}
+// after the count pass wrote this process's counts: every rank's counts, the
+// row offsets and the (empty) links.  slot: the links of a rank's share
+static int csr_place(psim_handle* h, hipStream_t st, ShCsr& c, uint32_t& slot) {
+    const uint32_t per = h->per, npad = per * h->G;
+    const uint32_t W = h->ranked ? (uint32_t)h->world : 1u, rper = h->ranked ? per : npad;
+    if (h->ranked) TRY(h->comm->all_gather(c.cnt.p + (size_t)h->rank * per, c.cnt.p, per, st));
+    // row offsets: a scan of all counts (entry npad: the total); a rank's
+    // rows are packed from the start of its slot, every slot as long as the
+    // largest rank's links, so the gathered CSR is the same everywhere
+    TRY(scan_excl(h->shards[0], c.cnt.p, c.off.p, npad + 1));
+    k_sh_rank_tot<<<1, 64, 0, st>>>(c.off.p, rper, W, npad, c.base.p, c.tot.p);
+    unsigned long long slot64 = 0;
+    HIP_TRY(hipMemcpyAsync(&slot64, c.tot.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (slot64 * W > 0xFFFFFFFFull) return PSIM_ENOMEM;       // (row offsets are 32-bit)
+    slot = (uint32_t)slot64;
+    if (W > 1) k_sh_shift<<<grid_for(npad), BLK, 0, st>>>(c.off.p, npad, rper, slot, c.base.p);
+    TRY(c.adj.alloc_on((size_t)slot * W, st));
+    return PSIM_OK;
+}
+// after the pack pass wrote this process's links: every rank's
+static int csr_gather(psim_handle* h, hipStream_t st, ShCsr& c, uint32_t slot) {
+    if (h->ranked && slot) TRY(h->comm->all_gather(c.adj.p + (size_t)h->rank * slot, c.adj.p, (size_t)slot * 4, st));
+    return PSIM_OK;
+}
+
 // sl: the SL_N words the count pass adds its per-node statistics to
 static int sh_build_csr(psim_handle* h, hipStream_t st, unsigned long long* sl, ShCsr& c) {
-    Shard* s0 = h->shards[0];
-    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
-    const uint32_t N = h->N, per = h->per, v2 = h->cfg.strategy == PSIM_STRATEGY_SCAMP_V2 ? 1u : 0u;
-    const uint32_t npad = per * h->G;
-    const uint32_t W = h->ranked ? (uint32_t)h->world : 1u, rper = h->ranked ? per : npad;
+    const uint8_t* fl = h->shards[0]->flags.p;   // replicated: every shard holds all N
+    const uint32_t N = h->N, v2 = h->cfg.strategy == PSIM_STRATEGY_SCAMP_V2 ? 1u : 0u;
     auto rows_grid = [](uint32_t n) { return (n + SH_NPB - 1) / SH_NPB; };
-    TmpBuf<uint8_t>& cnt = c.cnt;
-    TmpBuf<uint32_t>& off = c.off, & base = c.base, & adj = c.adj;
-    TmpBuf<unsigned long long>& tot = c.tot;
-    TRY(tot.alloc_on(1, st));
-    TRY(cnt.alloc_on((size_t)npad + 1, st)); TRY(off.alloc_on((size_t)npad + 1, st)); TRY(base.alloc_on(W, st));
+    TRY(csr_alloc(h, st, c));
     // 1. the row pass: per-node statistics, and the link count of every node
     for (Shard* s : h->shards)
         if (s->n)
-            k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, cnt.p, nullptr,
+            k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, c.cnt.p, nullptr,
                                                        nullptr, sl);
     HIP_TRY(hipGetLastError());
-    if (h->ranked) TRY(h->comm->all_gather(cnt.p + (size_t)h->rank * per, cnt.p, per, st));
-    // 2. row offsets: a scan of all counts (entry npad: the total); a rank's
-    // rows are packed from the start of its slot, every slot as long as the
-    // largest rank's links, so the gathered CSR is the same everywhere
-    TRY(scan_excl(s0, cnt.p, off.p, npad + 1));
-    k_sh_rank_tot<<<1, 64, 0, st>>>(off.p, rper, W, npad, base.p, tot.p);
-    unsigned long long slot64 = 0;
-    HIP_TRY(hipMemcpyAsync(&slot64, tot.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (slot64 * W > 0xFFFFFFFFull) return PSIM_ENOMEM;       // (row offsets are 32-bit)
-    const uint32_t slot = (uint32_t)slot64;
-    if (W > 1) k_sh_shift<<<grid_for(npad), BLK, 0, st>>>(off.p, npad, rper, slot, base.p);
-    TRY(adj.alloc_on((size_t)slot * W, st));
+    // 2. row offsets, then the pack pass
+    uint32_t slot = 0;
+    TRY(csr_place(h, st, c, slot));
     for (Shard* s : h->shards)
         if (s->n)
-            k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, cnt.p, off.p,
-                                                       adj.p, sl);
+            k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, c.cnt.p, c.off.p,
+                                                       c.adj.p, sl);
     HIP_TRY(hipGetLastError());
-    if (h->ranked && slot) TRY(h->comm->all_gather(adj.p + (size_t)h->rank * slot, adj.p, (size_t)slot * 4, st));
-    return PSIM_OK;
+    return csr_gather(h, st, c, slot);
 }
 
 int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) {
@@ -5984,6 +6255,144 @@ int psim_get_graph_metrics(psim_handle* h, const uint32_t* sources, size_t n_sou
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t j = 0; j < PSIM_GRAPH_SOURCES; j++) out->reach[j] = rv[j];
     out->pairs_unreached = out->sources_live * (out->n_up - 1) - out->pairs_reached;
+    return PSIM_OK;
+}
+
+// a single-source BFS from the live node `root` over the rows k_tm_bfs reads,
+// a kernel per level, the level's count read back after each (zero ends it),
+// at most `cap` levels.  depth: N words; lv: cap + 1 zeroed words; per[d]: the
+// nodes first found at level d; levels, truncated: as psim_graph_metrics' are
+static int tm_bfs(hipStream_t st, const uint32_t* off, const uint8_t* cnt, const uint32_t* adj, uint32_t N,
+                  uint32_t root, uint32_t cap, uint32_t* depth, unsigned long long* lv,
+                  std::vector<uint64_t>& per, uint64_t& levels, bool& truncated) {
+    HIP_TRY(hipMemsetAsync(depth, 0xFF, (size_t)N * 4, st));
+    HIP_TRY(hipMemsetAsync(depth + root, 0, 4, st));
+    per.assign(1, 0);
+    levels = 0;
+    for (uint32_t d = 1; d <= cap; d++) {
+        unsigned long long w = 0;
+        k_tm_bfs<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, N, d, depth, lv + d);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&w, lv + d, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        levels = d;
+        if (!w) break;
+        per.push_back(w);
+        if (d == cap) truncated = true;
+    }
+    return PSIM_OK;
+}
+
+// PSIM_TREE_LANES=64: a wave a node in k_tm_rows, for A/B (DESIGN.md
+// "Broadcast tree"); anything else: the 16-lane row
+static uint32_t tm_lanes() {
+    const char* e = getenv("PSIM_TREE_LANES");
+    return e && atoi(e) == 64 ? 64u : 16u;
+}
+
+int psim_get_tree_metrics(psim_handle* h, uint32_t root, uint32_t max_levels, psim_tree_metrics* out) {
+    if (!h || !out) return PSIM_EINVAL;
+    if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE || h->hosted || !h->cfg.plumtree)
+        return PSIM_EUNSUPPORTED;                // (hosted: a collective)
+    if (h->round_open) return PSIM_ESTATE;
+    if (root >= h->N) return PSIM_ERANGE;
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    memset(out, 0, sizeof *out);
+    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
+    Shard* s0 = h->shards[0];
+    hipStream_t st = s0->stream;
+    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
+    const uint32_t N = h->N, lanes = tm_lanes();
+    // 1. T as a CSR, the same on every rank, and the entry-level counts
+    ShCsr csr;
+    TmpBuf<unsigned long long> tm, tf, sym;
+    TmpBuf<uint32_t> indeg;
+    TRY(tm.alloc_on(TM_N, st)); TRY(tf.alloc_on(TF_N, st)); TRY(sym.alloc_on(1, st)); TRY(indeg.alloc_on(N, st));
+    TRY(csr_alloc(h, st, csr));
+    auto rows = [&](const uint32_t* off, uint32_t* adj) {
+        for (Shard* s : h->shards) {
+            if (!s->n) continue;
+            const uint32_t grid = (uint32_t)(((uint64_t)s->n * lanes + BLK - 1) / BLK);
+            if (lanes == 64)
+                k_tm_rows<64><<<grid, BLK, 0, st>>>(s->hdr.p, s->act.p, s->pt_rt.p, s->pt_eag.p, s->pt_laz.p,
+                                                    s->pt_com.p, fl, s->lo, s->n, N, root, csr.cnt.p, off, adj,
+                                                    indeg.p, tm.p);
+            else
+                k_tm_rows<16><<<grid, BLK, 0, st>>>(s->hdr.p, s->act.p, s->pt_rt.p, s->pt_eag.p, s->pt_laz.p,
+                                                    s->pt_com.p, fl, s->lo, s->n, N, root, csr.cnt.p, off, adj,
+                                                    indeg.p, tm.p);
+        }
+    };
+    rows(nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    uint32_t slot = 0;
+    TRY(csr_place(h, st, csr, slot));
+    rows(csr.off.p, csr.adj.p);
+    HIP_TRY(hipGetLastError());
+    TRY(csr_gather(h, st, csr, slot));
+    if (h->ranked) {
+        TRY(h->comm->all_reduce(tm.p, TM_N, CType::U64, COp::SUM, st));
+        TRY(h->comm->all_reduce(indeg.p, N, CType::U32, COp::SUM, st));
+    }
+    const uint32_t* off = csr.off.p;
+    const uint32_t* adj = csr.adj.p;
+    const uint8_t* cnt = csr.cnt.p;
+    k_tm_sym<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, N, sym.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long tv[TM_N], sv = 0;
+    uint8_t rf = 0;
+    HIP_TRY(hipMemcpyAsync(tv, tm.p, sizeof tv, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&sv, sym.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&rf, fl + root, 1, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < PSIM_HIST_BINS; k++) {
+        out->eager_out[k] = tv[TM_EOUT * PSIM_HIST_BINS + k];
+        out->lazy_out[k] = tv[TM_LOUT * PSIM_HIST_BINS + k];
+    }
+    out->n_up = tv[TM_NUP]; out->slot_nodes = tv[TM_SLOT];
+    out->eager_entries = tv[TM_EENT]; out->lazy_entries = tv[TM_LENT];
+    out->eager_links = tv[TM_ELINKS]; out->lazy_links = tv[TM_LLINKS]; out->both_links = tv[TM_BOTH];
+    out->eager_both_forms = tv[TM_FORMS]; out->self_entries = tv[TM_SELF];
+    out->eager_dead = tv[TM_EDEAD]; out->lazy_dead = tv[TM_LDEAD];
+    out->eager_nonmember = tv[TM_ENM]; out->lazy_nonmember = tv[TM_LNM];
+    out->eager_symmetric = sv;
+    out->root_live = (rf & F_UP) ? 1 : 0;
+    // 2. the two BFS passes from a live root: over T, then over the overlay's
+    // L (HyParView's gathered rows filtered as psim_get_graph_metrics does)
+    TmpBuf<uint32_t> dt, dl, gact, fadj;
+    TmpBuf<uint8_t> gan, fcnt;
+    TmpBuf<unsigned long long> lv;
+    if (out->root_live) {
+        const uint32_t cap = !max_levels || max_levels > PSIM_GRAPH_MAX_LEVELS ? PSIM_GRAPH_MAX_LEVELS : max_levels;
+        std::vector<uint64_t> per;
+        uint64_t levels = 0;
+        bool trunc = false;
+        TRY(dt.alloc_on(N, st)); TRY(dl.alloc_on(N, st)); TRY(lv.alloc_on(2 * ((size_t)cap + 1), st));
+        TRY(tm_bfs(st, off, cnt, adj, N, root, cap, dt.p, lv.p, per, levels, trunc));
+        out->levels = levels;
+        for (uint32_t d = 1; d < per.size(); d++) {
+            out->depth[d < PSIM_HIST_BINS ? d : PSIM_HIST_BINS - 1] += per[d];
+            out->depth_sum += (uint64_t)d * per[d];
+            out->reached += per[d];
+            out->depth_max = d;
+        }
+        TRY(gather_active_rows(h, st, gact, gan));
+        TRY(fadj.alloc_on((size_t)N * PSIM_ACTIVE_CAP, st)); TRY(fcnt.alloc_on(N, st));
+        k_gm_filter<<<grid_for(N), BLK, 0, st>>>(gan.p, gact.p, fl, N, fadj.p, fcnt.p);
+        TRY(tm_bfs(st, nullptr, fcnt.p, fadj.p, N, root, cap, dl.p, lv.p + cap + 1, per, levels, trunc));
+        out->truncated = trunc ? 1 : 0;
+        out->unreached = out->n_up - 1 - out->reached;
+    }
+    // 3. per node: the in-degree histogram, the two depths side by side
+    k_tm_final<<<grid_for(N), BLK, 0, st>>>(indeg.p, cnt, fl, N, root, dt.p, dl.p, tf.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long fv[TF_N];
+    HIP_TRY(hipMemcpyAsync(fv, tf.p, sizeof fv, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < PSIM_HIST_BINS; k++) out->eager_in[k] = fv[k];
+    out->links_from_reached = fv[TF_LFR]; out->overlay_reached = fv[TF_OREACH]; out->both_reached = fv[TF_BOTH];
+    out->depth_sum_both = fv[TF_DSUM]; out->dist_sum_both = fv[TF_LSUM];
+    out->deeper = fv[TF_DEEPER]; out->shallower = fv[TF_SHALLOWER];
     return PSIM_OK;
 }
 

@@ -436,6 +436,19 @@ class Simulator(_Driver):
         out["reach"], out["ecc"] = reach, ecc
         return out
 
+    def tree_metrics(self, root, max_levels=0):
+        """The broadcast tree of Plumtree root `root` (psim_tree_metrics) as a
+        dict of ints / arrays; a collective on rank handles."""
+        m = _abi.PsimTreeMetrics()
+        self._check(self._extra["get_tree_metrics"](self._h, int(root), max_levels, C.byref(m)), "get_tree_metrics")
+        out = {}
+        for name, _ in _abi.PsimTreeMetrics._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(m, name)
+            out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
+        return out
+
     # (k_node_prep: the quiet lazy ticks it counts without running the node)
     KERNELS = ("k_relay", "k_shuf", "k_lite_half", "k_consume", "k_ptl", "k_pt", "k_node_prep")
 
