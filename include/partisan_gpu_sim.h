@@ -452,6 +452,57 @@ typedef struct psim_tree_metrics {
     uint64_t reserved[8];
 } psim_tree_metrics;
 
+/* Broadcast reach under mass node failure, computed on the device (DESIGN.md
+ * "Reach under mass failure"): up to PSIM_FAIL_CASES failure cases in one
+ * bit-parallel BFS, bit j of a node's word = "in case j this node survived
+ * (and has been reached)".  A case fails a pseudo-random share of all nodes at
+ * one instant and floods from its source over what is left of the overlay,
+ * before any healing.  Everything is an integer, so the struct is bit-exact
+ * whatever the order of any sum.
+ *   u(v, salt) = (uint32_t)(mix64(fail_seed ^ mix64(((uint64_t)salt << 32) | v)) >> 32),
+ *     mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *     z *= 0x94D049BB133111EB; z ^= z >> 31 (64-bit, wrapping).
+ *   L: the link set psim_graph_metrics counts -- for HyParView and X-BOT
+ *     handles the active view, p != i, p live, repeats dropped; for SCAMP
+ *     v1 / v2 handles the distinct pairs of psim_strategy_histograms.links.
+ *   Case j is live if node source_j is up.  A dead source's case is skipped
+ *     and all its slots stay zero, as a dead source's are in
+ *     psim_graph_metrics.
+ *   A_j, the survivors of live case j: the up nodes v with v == source_j or
+ *     u(v, salt_j) >= threshold_j.  L_j: the links of L with both ends in A_j.
+ *   Liveness is the only other filter: partitions are ignored, as in every
+ *     statistics call.  The BFS runs levels d = 1, 2, ... while d <= the level
+ *     cap; a level that finds no node ends it.
+ * Not modelled: passive views and healing -- that experiment is psim_crash
+ * plus psim_step. */
+#define PSIM_FAIL_CASES 64
+typedef struct psim_failure_case {
+    uint32_t source;     /* the flood starts here; it never fails in its own case */
+    uint32_t threshold;  /* node v != source fails iff u(v, salt) < threshold: the failed share is threshold / 2^32 */
+    uint32_t salt;       /* cases with equal salts fail nested sets; different salts, independent ones */
+    uint32_t reserved;   /* 0 */
+} psim_failure_case;
+typedef struct psim_resilience {
+    uint64_t n_up;                           /* live nodes */
+    uint64_t links;                          /* |L| */
+    uint64_t cases_live;                     /* number of live cases */
+    uint64_t live_mask;                      /* bit j set: case j is live */
+    uint64_t alive[PSIM_FAIL_CASES];         /* |A_j| */
+    uint64_t links_alive[PSIM_FAIL_CASES];   /* |L_j| */
+    uint64_t no_out[PSIM_FAIL_CASES];        /* nodes of A_j with no out-link in L_j */
+    uint64_t no_in[PSIM_FAIL_CASES];         /* nodes of A_j with no in-link in L_j, the source included
+                                                if it has none: a flood can never reach these */
+    uint64_t reached[PSIM_FAIL_CASES];       /* nodes v != source_j at finite directed distance from
+                                                source_j over L_j; reliability = reached / (alive - 1) */
+    uint64_t hop_sum[PSIM_FAIL_CASES];       /* the exact sum of those distances */
+    uint64_t ecc[PSIM_FAIL_CASES];           /* the largest finite distance */
+    uint64_t ecc_max;                        /* the largest ecc[j] */
+    uint64_t levels;                         /* BFS levels run (the last one may have found nothing) */
+    uint64_t truncated;                      /* 1: the level cap ended the BFS with level `cap` still
+                                                finding a node; farther nodes count as not reached */
+    uint64_t reserved[8];
+} psim_resilience;
+
 typedef struct psim_handle psim_handle;
 
 void psim_default_config(psim_config *cfg);
@@ -618,6 +669,21 @@ int psim_get_graph_metrics(psim_handle *h, const uint32_t *sources, size_t n_sou
  * collective on rank handles (every rank calls with the same arguments; every
  * rank gets the same struct).  No Erlang binding yet. */
 int psim_get_tree_metrics(psim_handle *h, uint32_t root, uint32_t max_levels, psim_tree_metrics *out);
+/* Reach of a flood under up to PSIM_FAIL_CASES failure cases
+ * (psim_resilience above), on the device, for HyParView, X-BOT and SCAMP
+ * v1 / v2 handles of any shard count; slot j of every per-case array is
+ * cases[j].  Two cases may name the same source.  n_cases == 0 fills n_up and
+ * links only.  max_levels caps the BFS: 0 means PSIM_GRAPH_MAX_LEVELS, and
+ * larger values are clamped to it.  Errors, in this order: PSIM_EINVAL for a
+ * null h or out, null cases with n_cases > 0, n_cases > PSIM_FAIL_CASES or a
+ * non-zero `reserved`; PSIM_EUNSUPPORTED for full-membership and
+ * host-exchange handles; PSIM_ESTATE with a round open; PSIM_ERANGE for a
+ * source >= n_nodes (a dead source is legal and skipped).  Read-only: the
+ * rounds stepped after it are those of a run without it.  A collective on
+ * rank handles (every rank calls with the same arguments; every rank gets the
+ * same struct).  No Erlang binding yet. */
+int psim_get_resilience(psim_handle *h, const psim_failure_case *cases, size_t n_cases, uint64_t fail_seed,
+                        uint32_t max_levels, psim_resilience *out);
 /* Snapshot of the whole simulation state of this process (node rows,
  * in-flight messages, round, events not yet applied are not included):
  * with buf == NULL (or cap too small) only *need is set.  psim_restore

@@ -174,6 +174,25 @@ class PsimTreeMetrics(C.Structure):
     ]
 
 
+FAIL_CASES = 64
+
+
+class PsimFailureCase(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("threshold", C.c_uint32), ("salt", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PsimResilience(C.Structure):
+    _fields_ = [
+        ("n_up", C.c_uint64), ("links", C.c_uint64), ("cases_live", C.c_uint64), ("live_mask", C.c_uint64),
+        ("alive", C.c_uint64 * FAIL_CASES), ("links_alive", C.c_uint64 * FAIL_CASES),
+        ("no_out", C.c_uint64 * FAIL_CASES), ("no_in", C.c_uint64 * FAIL_CASES),
+        ("reached", C.c_uint64 * FAIL_CASES), ("hop_sum", C.c_uint64 * FAIL_CASES),
+        ("ecc", C.c_uint64 * FAIL_CASES),
+        ("ecc_max", C.c_uint64), ("levels", C.c_uint64), ("truncated", C.c_uint64),
+        ("reserved", C.c_uint64 * 8),
+    ]
+
+
 NODE_VIEW_DTYPE = np.dtype(PsimNodeView)
 STRATEGY_VIEW_DTYPE = np.dtype(PsimStrategyView)
 STATS_DTYPE = np.dtype(PsimRoundStats)
@@ -225,6 +244,8 @@ GPU_ONLY = {
     "get_strategy_histograms": (C.c_int, [_H, C.POINTER(PsimStrategyHistograms)]),
     "get_graph_metrics": (C.c_int, [_H, _P32, C.c_size_t, C.c_uint32, C.POINTER(PsimGraphMetrics)]),
     "get_tree_metrics": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(PsimTreeMetrics)]),
+    "get_resilience": (C.c_int, [_H, C.POINTER(PsimFailureCase), C.c_size_t, C.c_uint64, C.c_uint32,
+                                 C.POINTER(PsimResilience)]),
 }
 # the host boundary (host-exchange handles: sim.HostSim, wire.check)
 HOST_BOUNDARY = {

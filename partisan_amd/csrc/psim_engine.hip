@@ -2593,6 +2593,144 @@ __global__ void __launch_bounds__(BLK) k_gm_level(uint32_t n, unsigned long long
     if (threadIdx.x == 0) { atomicOr(&lv[0], sh_lv[0]); atomicAdd(&lv[1], sh_lv[1]); }
 }
 
+// ------------------------------------------- reach under mass failure --
+// psim_get_resilience (psim_resilience in the header defines every field):
+// the word of the k_gm_* BFS spent on 64 failure cases, bit j of alive[v] =
+// "v is in A_j".  The rows are those k_gm_push reads.
+//   k_rs_live     the mask of cases whose source is up
+//   k_rs_alive    alive[v], and the BFS seeded from it: seen[v] = ~alive[v]
+//                 plus the bits of the cases that start at v, front[v] = those
+//                 bits; a failed or down bit is never new to k_gm_level
+//   k_rs_census   over every link (i, p): m = alive[i] & alive[p] counted per
+//                 bit into links_alive, ORed into inw[p]; no_out from the
+//                 bits of alive[i] that no link kept
+//   k_rs_sweep    alive[] and no_in per bit
+// The case table `par`: RS_SRC, RS_THR and RS_SALT by the host's order (cases
+// of one salt side by side, so a node pays one inner mix64 per distinct salt),
+// RS_SLOT the slot of each.
+enum { RS_SRC = 0, RS_THR = 64, RS_SALT = 128, RS_SLOT = 192, RS_PAR = 256 };
+enum { RS_ALIVE = 0, RS_LINKS = 64, RS_NOOUT = 128, RS_NOIN = 192, RS_NUP = 256, RS_L = 257, RS_LIVE = 258, RS_N = 259 };
+
+DEV uint64_t rs_wave_or(uint64_t w) {
+    uint32_t lo = (uint32_t)w, hi = (uint32_t)(w >> 32);
+    for (int d = 32; d; d >>= 1) { lo |= (uint32_t)__shfl_xor((int)lo, d); hi |= (uint32_t)__shfl_xor((int)hi, d); }
+    return ((uint64_t)hi << 32) | lo;
+}
+// the wave's lanes holding bit j of w, for every j set in some lane, into the
+// block's 64-word tile: one ballot per such bit, as k_gm_level counts `reach`
+DEV void rs_tile_add(unsigned long long* tile, uint64_t w) {
+    uint64_t todo = rs_wave_or(w);                    // (uniform)
+    while (todo) {
+        const int j = ffs64(todo);
+        todo &= todo - 1;
+        const uint32_t c = popc(ballot((w >> j) & 1));
+        if (lane_id() == 0) atomicAdd(&tile[j], (unsigned long long)c);
+    }
+}
+
+__global__ void k_rs_live(const uint32_t* __restrict__ par, uint32_t nc, const uint8_t* __restrict__ flags,
+                          unsigned long long* rs) {
+    const uint32_t q = threadIdx.x;                   // (one block of 64 threads; the sources are < n)
+    const bool on = q < nc && (flags[par[RS_SRC + q]] & F_UP);
+    if (on) atomicOr(&rs[RS_LIVE], 1ull << par[RS_SLOT + q]);
+}
+
+__global__ void __launch_bounds__(BLK) k_rs_alive(const uint32_t* __restrict__ par, uint32_t nc, uint64_t fail_seed,
+                                                  const uint8_t* __restrict__ flags, uint32_t n,
+                                                  unsigned long long* rs, unsigned long long* alive,
+                                                  unsigned long long* seen, unsigned long long* front) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool up = v < n && (flags[v] & F_UP);
+    const unsigned long long live = rs[RS_LIVE];      // (k_rs_live ran before on the stream)
+    unsigned long long a = 0, sb = 0;
+    if (up) {
+        uint64_t inner = 0;
+        for (uint32_t q = 0; q < nc; q++) {           // (uniform)
+            const uint32_t salt = par[RS_SALT + q];
+            if (!q || salt != par[RS_SALT + q - 1]) inner = mix64(((uint64_t)salt << 32) | v);
+            const uint32_t u = (uint32_t)(mix64(fail_seed ^ inner) >> 32);
+            const unsigned long long bit = 1ull << par[RS_SLOT + q];
+            const bool src = par[RS_SRC + q] == v;
+            if (src || u >= par[RS_THR + q]) a |= bit;
+            if (src) sb |= bit;
+        }
+        a &= live; sb &= live;
+    }
+    if (v < n) { alive[v] = a; seen[v] = ~a | sb; front[v] = sb; }
+    const uint32_t c = popc(ballot(up));
+    if (c && lane_id() == 0) atomicAdd(&rs[RS_NUP], (unsigned long long)c);
+}
+
+__global__ void __launch_bounds__(BLK) k_rs_census(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
+                                                   const uint32_t* __restrict__ adj,
+                                                   const uint8_t* __restrict__ flags, uint32_t n,
+                                                   const unsigned long long* __restrict__ alive,
+                                                   unsigned long long* inw, unsigned long long* rs) {
+    static_assert(PSIM_SVIEW_CAP < 256 && PSIM_ACTIVE_CAP < 256, "a row's links per case fit the 8 counter planes");
+    __shared__ unsigned long long sh_links[PSIM_FAIL_CASES], sh_noout[PSIM_FAIL_CASES], sh_l;
+    if (threadIdx.x < PSIM_FAIL_CASES) { sh_links[threadIdx.x] = 0; sh_noout[threadIdx.x] = 0; }
+    if (threadIdx.x == 0) sh_l = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool up = i < n && (flags[i] & F_UP);
+    const uint32_t c = up ? cnt[i] : 0;
+    const unsigned long long a = up ? alive[i] : 0;
+    // plane b holds bit b of this node's link count of every case
+    unsigned long long pl[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ho = 0;
+    if (a) {
+        const uint32_t* row = adj + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP);
+        for (uint32_t k = 0; k < c; k++) {
+            const uint32_t p = row[k];
+            const unsigned long long m = a & alive[p];
+            if (!m) continue;
+            ho |= m;
+            if (m & ~inw[p]) atomicOr(&inw[p], m);
+            unsigned long long carry = m;
+#pragma unroll
+            for (int b = 0; b < 8; b++) { const unsigned long long t = pl[b] & carry; pl[b] ^= carry; carry = t; }
+        }
+    }
+    const uint32_t lsum = sh_wave_sum(c);
+    if (lsum && lane_id() == 0) atomicAdd(&sh_l, (unsigned long long)lsum);
+    if (ballot(a != 0)) {                             // (uniform)
+        rs_tile_add(sh_noout, a & ~ho);
+        uint64_t todo = rs_wave_or(ho);
+        while (todo) {
+            const int j = ffs64(todo);
+            todo &= todo - 1;
+            uint32_t s = 0;
+#pragma unroll
+            for (int b = 0; b < 8; b++) s += popc(ballot((pl[b] >> j) & 1)) << b;
+            if (lane_id() == 0) atomicAdd(&sh_links[j], (unsigned long long)s);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < PSIM_FAIL_CASES) {
+        if (sh_links[threadIdx.x]) atomicAdd(&rs[RS_LINKS + threadIdx.x], sh_links[threadIdx.x]);
+        if (sh_noout[threadIdx.x]) atomicAdd(&rs[RS_NOOUT + threadIdx.x], sh_noout[threadIdx.x]);
+    }
+    if (threadIdx.x == 0 && sh_l) atomicAdd(&rs[RS_L], sh_l);
+}
+
+__global__ void __launch_bounds__(BLK) k_rs_sweep(uint32_t n, const unsigned long long* __restrict__ alive,
+                                                  const unsigned long long* __restrict__ inw,
+                                                  unsigned long long* rs) {
+    __shared__ unsigned long long sh_alive[PSIM_FAIL_CASES], sh_noin[PSIM_FAIL_CASES];
+    if (threadIdx.x < PSIM_FAIL_CASES) { sh_alive[threadIdx.x] = 0; sh_noin[threadIdx.x] = 0; }
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long a = i < n ? alive[i] : 0;
+    if (ballot(a != 0)) {                             // (uniform)
+        rs_tile_add(sh_alive, a);
+        rs_tile_add(sh_noin, a & ~inw[i < n ? i : 0]);
+    }
+    __syncthreads();
+    if (threadIdx.x < PSIM_FAIL_CASES) {
+        if (sh_alive[threadIdx.x]) atomicAdd(&rs[RS_ALIVE + threadIdx.x], sh_alive[threadIdx.x]);
+        if (sh_noin[threadIdx.x]) atomicAdd(&rs[RS_NOIN + threadIdx.x], sh_noin[threadIdx.x]);
+    }
+}
+
 // ------------------------------------------------------ broadcast tree --
 // psim_get_tree_metrics: root R's eager / lazy sets of every live node
 // (psim_tree_metrics in the header defines every field).
@@ -6255,6 +6393,104 @@ int psim_get_graph_metrics(psim_handle* h, const uint32_t* sources, size_t n_sou
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t j = 0; j < PSIM_GRAPH_SOURCES; j++) out->reach[j] = rv[j];
     out->pairs_unreached = out->sources_live * (out->n_up - 1) - out->pairs_reached;
+    return PSIM_OK;
+}
+
+int psim_get_resilience(psim_handle* h, const psim_failure_case* cases, size_t n_cases, uint64_t fail_seed,
+                        uint32_t max_levels, psim_resilience* out) {
+    static_assert(PSIM_FAIL_CASES == 64 && PSIM_FAIL_CASES == PSIM_GRAPH_SOURCES,
+                  "one bit of k_gm_level's 64-bit word per case");
+    if (!h || !out || (n_cases && !cases) || n_cases > PSIM_FAIL_CASES) return PSIM_EINVAL;
+    const uint32_t nc = (uint32_t)n_cases;
+    for (uint32_t j = 0; j < nc; j++)
+        if (cases[j].reserved) return PSIM_EINVAL;
+    const bool pl = h->cfg.manager == PSIM_MANAGER_PLUGGABLE;
+    if (h->hosted || (pl && h->cfg.strategy == PSIM_STRATEGY_FULL)) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
+    if (h->round_open) return PSIM_ESTATE;
+    const uint32_t N = h->N;
+    for (uint32_t j = 0; j < nc; j++)
+        if (cases[j].source >= N) return PSIM_ERANGE;
+    // the case table: cases of one salt side by side (k_rs_alive)
+    uint32_t ord[PSIM_FAIL_CASES], par[RS_PAR] = {0};
+    for (uint32_t j = 0; j < nc; j++) ord[j] = j;
+    std::stable_sort(ord, ord + nc, [&](uint32_t a, uint32_t b) { return cases[a].salt < cases[b].salt; });
+    for (uint32_t q = 0; q < nc; q++) {
+        const psim_failure_case& c = cases[ord[q]];
+        par[RS_SRC + q] = c.source; par[RS_THR + q] = c.threshold; par[RS_SALT + q] = c.salt; par[RS_SLOT + q] = ord[q];
+    }
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    memset(out, 0, sizeof *out);
+    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
+    Shard* s0 = h->shards[0];
+    hipStream_t st = s0->stream;
+    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
+    // 1. the link set as rows, as psim_get_graph_metrics reads it
+    ShCsr csr;
+    TmpBuf<unsigned long long> sl, rs;
+    TmpBuf<uint32_t> gact, fadj, dpar;
+    TmpBuf<uint8_t> gan, fcnt;
+    const uint32_t* off = nullptr;
+    const uint32_t* adj = nullptr;
+    const uint8_t* cnt = nullptr;
+    if (pl) {
+        TRY(sl.alloc_on(SL_N, st));              // (the count pass's statistics: not reported here)
+        TRY(sh_build_csr(h, st, sl.p, csr));
+        off = csr.off.p; adj = csr.adj.p; cnt = csr.cnt.p;
+    } else {
+        TRY(gather_active_rows(h, st, gact, gan));
+        TRY(fadj.alloc_on((size_t)N * PSIM_ACTIVE_CAP, st)); TRY(fcnt.alloc_on(N, st));
+        k_gm_filter<<<grid_for(N), BLK, 0, st>>>(gan.p, gact.p, fl, N, fadj.p, fcnt.p);
+        adj = fadj.p; cnt = fcnt.p;
+    }
+    // 2. the survivor words (they seed the BFS) and the census
+    const uint32_t cap = !max_levels || max_levels > PSIM_GRAPH_MAX_LEVELS ? PSIM_GRAPH_MAX_LEVELS : max_levels;
+    TmpBuf<unsigned long long> alive, seen, front, next, lv, reach;
+    TRY(rs.alloc_on(RS_N, st)); TRY(dpar.alloc_on(RS_PAR, st));
+    TRY(alive.alloc_on(N, st)); TRY(seen.alloc_on(N, st)); TRY(front.alloc_on(N, st)); TRY(next.alloc_on(N, st));
+    HIP_TRY(hipMemcpyAsync(dpar.p, par, sizeof par, hipMemcpyHostToDevice, st));
+    k_rs_live<<<1, 64, 0, st>>>(dpar.p, nc, fl, rs.p);
+    k_rs_alive<<<grid_for(N), BLK, 0, st>>>(dpar.p, nc, fail_seed, fl, N, rs.p, alive.p, seen.p, front.p);
+    // (next: the in-link words until the BFS needs it zeroed again)
+    k_rs_census<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, fl, N, alive.p, next.p, rs.p);
+    if (nc) k_rs_sweep<<<grid_for(N), BLK, 0, st>>>(N, alive.p, next.p, rs.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long rv[RS_N];
+    HIP_TRY(hipMemcpyAsync(rv, rs.p, sizeof rv, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->n_up = rv[RS_NUP]; out->links = rv[RS_L];
+    const unsigned long long live = rv[RS_LIVE];
+    out->live_mask = live; out->cases_live = (uint64_t)__builtin_popcountll(live);
+    for (uint32_t j = 0; j < PSIM_FAIL_CASES; j++) {
+        out->alive[j] = rv[RS_ALIVE + j]; out->links_alive[j] = rv[RS_LINKS + j];
+        out->no_out[j] = rv[RS_NOOUT + j]; out->no_in[j] = rv[RS_NOIN + j];
+    }
+    if (!live) return PSIM_OK;
+    // 3. the BFS of psim_get_graph_metrics over the seeded words: reach[]
+    // comes back with each level's words, its growth times d is the hop sum
+    TRY(lv.alloc_on(2 * ((size_t)cap + 1), st)); TRY(reach.alloc_on(PSIM_GRAPH_SOURCES, st));
+    HIP_TRY(hipMemsetAsync(next.p, 0, (size_t)N * 8, st));
+    unsigned long long prev[PSIM_FAIL_CASES] = {0}, cur[PSIM_FAIL_CASES] = {0};
+    for (uint32_t d = 1; d <= cap; d++) {
+        unsigned long long w[2] = {0, 0};
+        k_gm_push<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, N, front.p, seen.p, next.p);
+        k_gm_level<<<grid_for(N), BLK, 0, st>>>(N, next.p, seen.p, front.p, lv.p + 2 * (size_t)d, reach.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(w, lv.p + 2 * (size_t)d, sizeof w, hipMemcpyDeviceToHost, st));
+#ifndef PSIM_RS_NO_REACH_COPY                    // (timing only, `make evariant`: what this copy costs a level)
+        HIP_TRY(hipMemcpyAsync(cur, reach.p, sizeof cur, hipMemcpyDeviceToHost, st));
+#endif
+        HIP_TRY(hipStreamSynchronize(st));
+        out->levels = d;
+        if (!w[0]) break;
+        for (uint32_t j = 0; j < PSIM_FAIL_CASES; j++) {
+            if (!((w[0] >> j) & 1)) continue;
+            out->hop_sum[j] += (uint64_t)d * (cur[j] - prev[j]);
+            out->reached[j] = prev[j] = cur[j];
+            out->ecc[j] = d;
+        }
+        out->ecc_max = d;
+        if (d == cap) out->truncated = 1;
+    }
     return PSIM_OK;
 }
 

@@ -449,6 +449,31 @@ class Simulator(_Driver):
             out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
         return out
 
+    def resilience(self, sources, thresholds, salts=None, fail_seed=0, max_levels=0):
+        """Reach of a flood under up to 64 failure cases (psim_resilience) as
+        a dict of ints / arrays; a collective on rank handles.  Case j floods
+        from sources[j] after every other node v with u(v, salts[j]) <
+        thresholds[j] has failed: the failed share is thresholds[j] / 2^32.
+        salts=None means all 0 (nested failure sets)."""
+        src = np.ascontiguousarray(sources, np.uint32).reshape(-1)
+        thr = np.ascontiguousarray(thresholds, np.uint32).reshape(-1)
+        slt = np.zeros(src.size, np.uint32) if salts is None else np.ascontiguousarray(salts, np.uint32).reshape(-1)
+        if not src.size == thr.size == slt.size:
+            raise ValueError("sources, thresholds and salts differ in length")
+        cases = (_abi.PsimFailureCase * max(src.size, 1))()
+        for j in range(src.size):
+            cases[j].source, cases[j].threshold, cases[j].salt = int(src[j]), int(thr[j]), int(slt[j])
+        m = _abi.PsimResilience()
+        self._check(self._extra["get_resilience"](self._h, cases if src.size else None, src.size, int(fail_seed),
+                                                  max_levels, C.byref(m)), "get_resilience")
+        out = {}
+        for name, _ in _abi.PsimResilience._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(m, name)
+            out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
+        return out
+
     # (k_node_prep: the quiet lazy ticks it counts without running the node)
     KERNELS = ("k_relay", "k_shuf", "k_lite_half", "k_consume", "k_ptl", "k_pt", "k_node_prep")
 
