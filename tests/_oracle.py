@@ -19,9 +19,13 @@ def load():
     global _lib
     if _lib is None:
         src = os.path.join(ORC_DIR, "psim_oracle.c")
-        if not os.path.exists(ORC_PATH) or os.path.getmtime(ORC_PATH) < os.path.getmtime(src):
+        # PSIM_ORACLE_LIB: another build of the same source, e.g. the coverage
+        # tool's instrumented one (tests/_oracle_coverage.py); never rebuilt here
+        path = os.environ.get("PSIM_ORACLE_LIB") or ORC_PATH
+        if path == ORC_PATH and (not os.path.exists(ORC_PATH) or
+                                 os.path.getmtime(ORC_PATH) < os.path.getmtime(src)):
             subprocess.check_call(["make", "-s", "-C", ORC_DIR])
-        _lib = C.CDLL(ORC_PATH)
+        _lib = C.CDLL(path)
         _lib.orc_get_inbox.restype = C.c_int
         _lib.orc_get_inbox.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.POINTER(C.c_size_t)]

@@ -688,3 +688,135 @@ def pl_v1_large_view(make, n=180, seed=29, per_round=20, leave_from=40, leave_to
                 sim.leave_node(np.array([0], np.uint32), np.array([row[len(row) // 2]], np.uint32))
     st = sim.run_schedule(sched, rounds, extra=hook)
     return sim, st, trace
+
+
+# ---- scenarios written for one oracle outcome each: the protocol outcomes no
+# other parity run takes (tests/_oracle_coverage.py finds them,
+# tests/_parity_registry.py names the outcome of each)
+def retired_ids(make, n=256, seed=3, first=20, part_on=30, part_off=70, rounds=90, **cfg):
+    """Retired Plumtree ids in flight: nodes 0 and 1 each broadcast every
+    round from `first`, ids counting up, so an id's slot is taken again 32
+    rounds later; a half/half partition over part_on..part_off - 1 keeps the
+    lazy pushes across it outstanding past that.  After the heal the lazy
+    tick sends IHAVEs of retired ids (msg_root: the stale-slot overflow, root
+    PSIM_NONE on the wire) and their receivers answer stale (pt_have)."""
+    sim = make(default_config(n_nodes=n, seed=seed, **cfg))
+    state = {"k": 0}
+
+    def hook(r):
+        if r == part_on:
+            sim.set_partition(W.half_partition(n))
+        if r == part_off:
+            sim.clear_partition()
+        if r >= first:
+            for root in (0, 1):
+                sim.broadcast(root, state["k"] % 0x10000)
+                state["k"] += 1
+    st = sim.run_schedule(W.doubling_join(n, seed), rounds, extra=hook)
+    return sim, st
+
+
+def same_id_again(make, n=256, seed=3, first=24, period=3, part_on=30, part_off=60, rounds=80, **cfg):
+    """One message id broadcast again and again, by roots 0, 1, 2 in turn,
+    every `period` rounds, through a half/half partition: a lazy push across
+    the partition stays outstanding while the next broadcast of the same id
+    reaches the node over another path, so its table holds one (peer, id)
+    under two rounds (pt_add_out's round compare) and an IGNORED_IHAVE meets
+    an entry that matches peer and id but not the round (pt_ack_out)."""
+    sim = make(default_config(n_nodes=n, seed=seed, **cfg))
+
+    def hook(r):
+        if r == part_on:
+            sim.set_partition(W.half_partition(n))
+        if r == part_off:
+            sim.clear_partition()
+        if r >= first and (r - first) % period == 0:
+            sim.broadcast(((r - first) // period) % 3, 5)
+    st = sim.run_schedule(W.doubling_join(n, seed), rounds, extra=hook)
+    return sim, st
+
+
+def graft_miss(make, n=256, seed=3, first=20, restart_at=(30, 34, 38), rounds=50, **cfg):
+    """A GRAFT for a message its receiver does not hold (backend graft/1 ->
+    {error, not_found}: no answer): node 0 broadcasts every round; a third of
+    the other nodes restart (psim_join of live nodes through node 0) one
+    round after their lazy ticks sent IHAVEs, so the GRAFTs those draw reach
+    a fresh incarnation."""
+    sim = make(default_config(n_nodes=n, seed=seed, **cfg))
+    state = {"k": 0}
+
+    def hook(r):
+        if r in restart_at:
+            ids = np.arange(1 + restart_at.index(r), n, 3, dtype=np.uint32)
+            sim.join(ids, np.zeros(ids.size, np.uint32))
+        if r >= first:
+            sim.broadcast(0, state["k"] % 0x10000)
+            state["k"] += 1
+    st = sim.run_schedule(W.doubling_join(n, seed), rounds, extra=hook)
+    return sim, st
+
+
+def full_leave_absent(make, n=24, started=12, seed=8, fanout=0, leave_at=20, rounds=40):
+    """leave/1 under the full strategy of a target the actor does not have
+    (full:58-89: no mutation, the gossip still goes out) beside one it does:
+    only the ids below `started` ever start; at leave_at node 1 removes
+    n - 1 (never a member), node 2 removes node 3 (a member), node 4 removes
+    node 3 a round later (already tombstoned in the merged state or not)."""
+    sim = make(default_config(n_nodes=n, seed=seed, manager=1, strategy=0, fanout=fanout))
+
+    def hook(r):
+        if r == leave_at:                       # (two calls before one step: both stay pending)
+            sim.leave_node(np.array([1], np.uint32), np.array([n - 1], np.uint32))
+            sim.leave_node(np.array([2], np.uint32), np.array([3], np.uint32))
+        if r == leave_at + 1:
+            sim.leave_node(np.array([4], np.uint32), np.array([3], np.uint32))
+    st = sim.run_schedule(W.doubling_join(started, seed), rounds, extra=hook)
+    return sim, st
+
+
+def pending_keep(make, n=400, seed=1, x=1, a=2, rejoin_at=28, rounds=72):
+    """The `pending` arm of the pluggable send check (SCAMP v2): node a joins
+    through x, and x restarts in the round a's hello arrives, so the hello is
+    lost and x stays a's pending contact.  Every other node then joins
+    through a, whose view fills to PSIM_SVIEW_CAP (it keeps about half of
+    the subscriptions).  From rejoin_at x joins through a every four rounds:
+    when a keeps x's subscription (4 draws in 10) it cannot store it (a
+    counted overflow) and sends keep_subscription to x -- no member of its
+    view, but its pending node."""
+    sim = make(default_config(n_nodes=n, seed=seed, manager=1, strategy=2))
+    none = np.array([W.NONE], np.uint32)
+    sched = [(0, np.array([x], np.uint32), none), (1, np.array([a], np.uint32), np.array([x], np.uint32)),
+             (2, np.array([x], np.uint32), none)]
+    rest = np.array([i for i in range(n) if i not in (x, a)], np.uint32)
+    per = 20
+    for k, lo in enumerate(range(0, rest.size, per)):
+        ids = rest[lo:lo + per]
+        sched.append((4 + k, ids, np.full(ids.size, a, np.uint32)))
+    assert 4 + len(sched) < rejoin_at < rounds
+
+    def hook(r):
+        if r >= rejoin_at and r % 4 == 0:
+            sim.join(np.array([x], np.uint32), np.array([a], np.uint32))
+    st = sim.run_schedule(sched, rounds, extra=hook)
+    return sim, st
+
+
+def epoch_refusal(make, **cfg):
+    """A FORWARD_JOIN refused by the integer-epoch clause of is_addable/3
+    (hyparview:1670-1676) where no forward target is left (hv:870-897):
+    event_edges with persisted epochs and active views of three, so that a
+    node restarted more often than the joiner, which has sent the joiner a
+    DISCONNECT in its present life, is the walk's dead end."""
+    return event_edges(make, persist_epoch=1, max_active_size=3, **cfg)
+
+
+def set_pool_full(make, n=64, seed=17, rounds=150, **cfg):
+    """A full per-root set pool (PSIM_PT_SET_POOL entries over a node's root
+    slots): four roots broadcasting every round under X-BOT's optimization
+    rounds every second round, active views of eight and 10 % churn -- the
+    lazy sets collect the identities of every sender since the last reset
+    (plumtree:599-609) until an add finds the pool full (counted as
+    PSIM_OVF_PT, the sets left as they were).  The ids pass the 64 message
+    slots every 16 rounds, so retired ids are in flight throughout."""
+    return multi_root(make, n=n, seed=seed, roots=4, rounds=rounds, period=1, first=10, churn=True,
+                      max_active_size=8, min_active_size=8, manager=2, xbot_period=2, **cfg)

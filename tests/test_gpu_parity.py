@@ -5,6 +5,7 @@ node's full state after the run must be identical."""
 import numpy as np
 import pytest
 
+import _parity_registry as P
 import _scenarios as S
 from _oracle import Oracle
 
@@ -29,34 +30,35 @@ def test_gpu_loads_native_library():
 
 
 def test_config_a_parity():
-    (gs, gst), (os_, ost) = _both(S.config_a)
+    (gs, gst), (os_, ost) = _both(P.PARITY["config_a"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_doubling_parity(seed):
-    (gs, gst), (os_, ost) = _both(S.doubling, 1024, seed, 60, bcast_period=10, bcast_first=25)
+    (gs, gst), (os_, ost) = _both(P.PARITY[f"doubling_{seed}"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
 def test_churn_partition_parity():
-    (gs, gst), (os_, ost) = _both(S.churn_partition, n=2048)
+    (gs, gst), (os_, ost) = _both(P.PARITY["churn_partition"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(period=1, snap_at=(60, 79))], ids=["tail", "at_cap"])
-def test_outstanding_tail_parity(kw):
+@pytest.mark.parametrize("run", ["out_tail", "out_tail_at_cap"], ids=["tail", "at_cap"])
+def test_outstanding_tail_parity(run):
     """Outstanding tables past one 64-lane register (up to PSIM_PT_OUT_CAP
     128; tests/test_out_tail.py shows the oracle fills them): adds, acks
     and lazy ticks over the extension row's tail, GPU == oracle, the tables
     compared while at their largest.  (neighbors_down/2's filter over a
-    tail, out_drop_peer, is not reached: the entries are lazy-set peers,
-    node_spec identities, and the filter drops bare ids -- DESIGN.md 2's
-    leak.)"""
-    (gs, gst, gsn), (os_, ost, osn) = _both(S.out_tail, **kw)
+    tail, out_drop_peer, runs but drops nothing, here and in every other
+    parity run: the entries are lazy-set peers, node_spec identities, and
+    the filter drops bare ids -- DESIGN.md 2's leak; the `notify` entries of
+    tests/golden/oracle_unreached.json.)"""
+    (gs, gst, gsn), (os_, ost, osn) = _both(P.PARITY[run])
     S.compare_stats(gst, ost)
     for r in osn:
         S.compare_nodes(gsn[r], osn[r])
@@ -69,8 +71,8 @@ def test_outstanding_pool_growth(monkeypatch):
     rows, with no overflow and GPU == oracle through the tables' largest
     (a snapshot of the grown pool restores into a fresh handle)"""
     monkeypatch.setenv("PSIM_OUTX_ROWS", "8")
-    gs, gst, gsn = S.out_tail(_gpu)
-    os_, ost, osn = S.out_tail(Oracle)
+    gs, gst, gsn = P.PARITY["out_tail"](_gpu)
+    os_, ost, osn = P.PARITY["out_tail"](Oracle)
     S.compare_stats(gst, ost)
     for r in osn:
         S.compare_nodes(gsn[r], osn[r])
@@ -112,7 +114,7 @@ def test_lingering_connections_parity():
     terminals' Senders, rejected and pending neighbor requests, a joiner's
     contact -- in the connection table, EXIT at every holder, Plumtree sends
     over them: the crash of the most-held lingering peers, GPU == oracle."""
-    (gs, gst, gv), (os_, ost, ov) = _both(S.lingering_exits)
+    (gs, gst, gv), (os_, ost, ov) = _both(P.PARITY["lingering_exits"])
     assert gv == ov and ov
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
@@ -122,19 +124,19 @@ def test_lingering_connections_parity():
 def test_e_miniature_parity():
     """Config E in miniature (bench.py's sharding-check schedule) at 2^14
     nodes: churn, restarts, a partition and broadcasts, GPU == oracle."""
-    (gs, gst), (os_, ost) = _both(S.e_miniature)
+    (gs, gst), (os_, ost) = _both(P.PARITY["e_miniature"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
 def test_crash_parity():
-    (gs, gst, _), (os_, ost, _) = _both(S.crash_only)
+    (gs, gst, _), (os_, ost, _) = _both(P.PARITY["crash_only"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
 def test_crash_revive_parity():
-    (gs, gst, _), (os_, ost, _) = _both(S.crash_revive)
+    (gs, gst, _), (os_, ost, _) = _both(P.PARITY["crash_revive"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
@@ -145,14 +147,13 @@ def test_star_hotspot_parity(n):
     their route bucket's fixed region (k_bucket_fill: 1.5x the bucket's
     share of the route capacity) and that round goes through the four-pass
     route again"""
-    (gs, gst), (os_, ost) = _both(S.star, n=n)
+    (gs, gst), (os_, ost) = _both(P.PARITY[{512: "star_512", 1 << 16: "star_64k"}[n]])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
 def test_variants_parity():
-    kw = dict(max_active_size=8, max_passive_size=20, arwl=6, prwl=6, persist_epoch=1)
-    (gs, gst), (os_, ost) = _both(S.churn_partition, n=1024, seed=13, rounds=110, **kw)
+    (gs, gst), (os_, ost) = _both(P.PARITY["variants"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
@@ -163,18 +164,14 @@ def test_forward_join_revert_parity(seed):
     the passive view, found no forward target and could not reach the
     joiner returns State0 -- the insert is undone, its draw stays consumed.
     Variant config (arwl = prwl = 6) with joiners crashing mid-walk."""
-    (gs, gst), (os_, ost) = _both(S.joiner_crash, seed=seed, **S.VARIANT)
+    (gs, gst), (os_, ost) = _both(P.PARITY[f"joiner_crash_{seed}"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
 def test_64k_parity():
     """2^16 nodes, 60 rounds + a broadcast: still cheap for the oracle (~5 s)."""
-    def run(make):
-        sim, st = S.doubling(make, 1 << 16, 21, 60)
-        sim.broadcast(0, 5)
-        return sim, np.concatenate([st, sim.step(40)])
-    (gs, gst), (os_, ost) = _both(run)
+    (gs, gst), (os_, ost) = _both(P.PARITY["doubling_64k"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
@@ -220,8 +217,8 @@ def test_shard_count_invariance(shards):
     def gpu_sharded(cfg):
         cfg.n_shards = shards
         return _gpu(cfg)
-    gs, gst = S.churn_partition(gpu_sharded, n=2048)
-    os_, ost = S.churn_partition(Oracle, n=2048)
+    gs, gst = P.PARITY["churn_partition"](gpu_sharded)
+    os_, ost = P.PARITY["churn_partition"](Oracle)
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
     # the wire format: 32 B a record, 32 more for one with exchange ids
@@ -242,17 +239,14 @@ def test_shard_invariance_multistep_blocks(shards, monkeypatch):
     def gpu_sharded(cfg):
         cfg.n_shards = shards
         return _gpu(cfg)
-    gs, gst = S.churn_partition(gpu_sharded, n=4096)
-    os_, ost = S.churn_partition(Oracle, n=4096)
+    gs, gst = P.PARITY["churn_partition_4096"](gpu_sharded)
+    os_, ost = P.PARITY["churn_partition_4096"](Oracle)
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
 def test_shard_invariance_64k():
-    def run(make):
-        sim, st = S.doubling(make, 1 << 16, 21, 60)
-        sim.broadcast(0, 5)
-        return sim, np.concatenate([st, sim.step(30)])
+    run = P.PARITY["doubling_64k_shards"]
 
     def g1(cfg):
         return _gpu(cfg)
@@ -268,8 +262,8 @@ def test_shard_invariance_64k():
 # ---- pluggable manager + membership strategies
 @pytest.mark.parametrize("strategy,n,fanout", [(0, 16, 0), (0, 2048, 5), (1, 2048, 0), (2, 2048, 0)])
 def test_strategy_parity(strategy, n, fanout):
-    (gs, gst), (os_, ost) = _both(S.pl_doubling, n, 11, 100, strategy=strategy, fanout=fanout,
-                                  crash_at=40, part_at=60)
+    (gs, gst), (os_, ost) = _both(P.PARITY[f"strategy_{strategy}_{n}"])
+    assert gs.cfg.fanout == fanout
     S.compare_stats(gst, ost)
     S.compare_strategy(gs, os_, full_bits=[0, 1, n // 2, n - 1] if strategy == 0 else None)
 
@@ -279,8 +273,7 @@ def test_strategy_leave_parity(strategy):
     """psim_leave (leave/0: the manager stops before its leave messages go
     out) at round 40 for 10% of the nodes, then a partition: bit-identical
     to the oracle."""
-    kw = dict(strategy=strategy, fanout=5 if strategy == 0 else 0, crash_at=40, part_at=60, leave=True)
-    (gs, gst), (os_, ost) = _both(S.pl_doubling, 1024, 11, 90, **kw)
+    (gs, gst), (os_, ost) = _both(P.PARITY[f"strategy_leave_{strategy}"])
     S.compare_stats(gst, ost)
     S.compare_strategy(gs, os_, full_bits=[0, 1, 512, 1023] if strategy == 0 else None)
 
@@ -293,9 +286,9 @@ def test_strategy_remote_leave_parity(strategy):
     def sharded(cfg):
         cfg.n_shards = 4
         return _gpu(cfg)
-    os_, ost, _, _ = S.pl_leave_remote(Oracle, 2048, 7, 90, strategy=strategy, part_at=60)
+    os_, ost, _, _ = P.PARITY[f"remote_leave_{strategy}"](Oracle)
     for make in (_gpu, sharded):
-        gs, gst, _, _ = S.pl_leave_remote(make, 2048, 7, 90, strategy=strategy, part_at=60)
+        gs, gst, _, _ = P.PARITY[f"remote_leave_{strategy}"](make)
         S.compare_stats(gst, ost)
         S.compare_strategy(gs, os_)
 
@@ -308,10 +301,11 @@ def test_omission_fault_parity(strategy, n, fanout):
     def sharded(cfg):
         cfg.n_shards = 4
         return _gpu(cfg)
-    os_, ost, _ = S.pl_omission(Oracle, n, 23, 100, strategy, fanout)
+    os_, ost, _ = P.PARITY[f"omission_{strategy}_{n}"](Oracle)
+    assert os_.cfg.fanout == fanout
     assert ost["omitted"].sum() > 0
     for make in (_gpu, sharded) if strategy else (_gpu,):
-        gs, gst, _ = S.pl_omission(make, n, 23, 100, strategy, fanout)
+        gs, gst, _ = P.PARITY[f"omission_{strategy}_{n}"](make)
         S.compare_stats(gst, ost)
         S.compare_strategy(gs, os_, full_bits=[0, 1, n // 2, n - 1] if strategy == 0 else None)
 
@@ -322,9 +316,9 @@ def test_full_remote_leave_parity(n, fanout):
     merged with the adds, the two-row gossip payload, a target stopping on a
     merged removal of itself -- bit-identical to the oracle (full-strategy
     handles are single-shard: gossip payloads are shard-local)."""
-    kw = dict(strategy=0, fanout=fanout, k=4, part_at=60)
-    os_, ost, _, _ = S.pl_leave_remote(Oracle, n, 8, 90, **kw)
-    gs, gst, _, _ = S.pl_leave_remote(_gpu, n, 8, 90, **kw)
+    os_, ost, _, _ = P.PARITY[f"full_remote_leave_{n}"](Oracle)
+    gs, gst, _, _ = P.PARITY[f"full_remote_leave_{n}"](_gpu)
+    assert gs.cfg.fanout == fanout
     S.compare_stats(gst, ost)
     S.compare_strategy(gs, os_, full_bits=[0, 1, n // 2, n - 1])
 
@@ -334,14 +328,14 @@ def test_strategy_shard_invariance(strategy):
     def sharded(cfg):
         cfg.n_shards = 4
         return _gpu(cfg)
-    gs, gst = S.pl_doubling(sharded, 4096, 12, 80, strategy=strategy, crash_at=40)
-    os_, ost = S.pl_doubling(Oracle, 4096, 12, 80, strategy=strategy, crash_at=40)
+    gs, gst = P.PARITY[f"strategy_shards_{strategy}"](sharded)
+    os_, ost = P.PARITY[f"strategy_shards_{strategy}"](Oracle)
     S.compare_stats(gst, ost)
     S.compare_strategy(gs, os_)
 
 
 def test_strategy_64k_parity():
-    (gs, gst), (os_, ost) = _both(S.pl_doubling, 1 << 16, 13, 60, strategy=2)
+    (gs, gst), (os_, ost) = _both(P.PARITY["strategy_64k"])
     S.compare_stats(gst, ost)
     S.compare_strategy(gs, os_)
 
@@ -356,17 +350,8 @@ def test_gpu_matches_committed_oracle_traces():
     sys.path.insert(0, os.path.join(here, "golden"))
     import gen_oracle_traces as G
     golden = json.load(open(os.path.join(here, "golden", "oracle_traces.json")))["traces"]
-    scen = {
-        "config_a": lambda: S.config_a(_gpu),
-        "churn_partition_1024": lambda: S.churn_partition(_gpu, n=1024),
-        "full_16_fanout0": lambda: S.pl_doubling(_gpu, 16, 11, 80, strategy=0, fanout=0, crash_at=40),
-        "full_1024_fanout5": lambda: S.pl_doubling(_gpu, 1024, 11, 80, strategy=0, fanout=5, part_at=50),
-        "scamp_v1_1024": lambda: S.pl_doubling(_gpu, 1024, 11, 100, strategy=1, crash_at=40, part_at=60),
-        "scamp_v2_1024": lambda: S.pl_doubling(_gpu, 1024, 11, 100, strategy=2, crash_at=40, part_at=60),
-        "scamp_v1_leave_1024": lambda: S.pl_leave_remote(_gpu, 1024, 7, 90, strategy=1, part_at=60)[:2],
-        "scamp_v2_leave_1024": lambda: S.pl_leave_remote(_gpu, 1024, 7, 90, strategy=2, part_at=60)[:2],
-        "full_leave_1024_fanout5": lambda: S.pl_leave_remote(_gpu, 1024, 8, 90, strategy=0, fanout=5, k=4)[:2],
-    }
+    scen = {name: (lambda name: lambda: P.PARITY["config_a" if name == "config_a" else "trace_" + name](_gpu)[:2])(name)
+            for name in G.SCENARIOS}
     assert set(scen) == set(G.SCENARIOS)
     for name, run in scen.items():
         _, st = run()
@@ -380,7 +365,7 @@ def test_route_regrow_parity(monkeypatch):
     the host's regrow and the reroute of the same outbox in most early
     rounds (PSIM_RCAP_INIT, psim_engine.hip); results stay bit-identical."""
     monkeypatch.setenv("PSIM_RCAP_INIT", "16")
-    (gs, gst), (os_, ost) = _both(S.doubling, 1024, 4, 40, bcast_period=10, bcast_first=15)
+    (gs, gst), (os_, ost) = _both(P.PARITY["route_regrow"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
@@ -394,13 +379,7 @@ def test_batch_regrow_parity(monkeypatch):
     monkeypatch.setenv("PSIM_NO_RESERVE", "1")
     monkeypatch.setenv("PSIM_RCAP_INIT", "16")
 
-    def run(make):
-        sim, _ = S.doubling(make, 4096, 9, 30, bcast_period=0, bcast_first=0)
-        sim.broadcast(7, 1)
-        out = [sim.step(60)]                      # one step call: batches, growth inside
-        sim.crash(np.arange(3, 4096, 37, dtype=np.uint32))
-        out.append(sim.step(40))
-        return sim, out
+    run = P.PARITY["batch_regrow"]             # (one step call of 60 rounds: batches, growth inside)
     (gs, gst), (os_, ost) = run(_gpu), run(Oracle)
     for a, b in zip(gst, ost):
         S.compare_stats(a, b)
@@ -411,12 +390,7 @@ def test_histograms_delivery_parity():
     """psim_get_histograms / psim_get_delivery: the GPU's device kernels
     (in-degree atomics, reverse-link test, label propagation) against the
     oracle's list-style statistics on the same run."""
-    def run(make):
-        sim, _ = S.doubling(make, 2048, 3, 70, bcast_period=25, bcast_first=30)
-        sim.crash(np.arange(5, 2048, 61, dtype=np.uint32))
-        sim.step(2)
-        return sim
-    g, o = run(_gpu), run(Oracle)
+    g, o = P.PARITY["histograms"](_gpu)[0], P.PARITY["histograms"](Oracle)[0]
     hg, ho = g.histograms(), o.histograms()
     for k in ho:
         assert np.array_equal(np.asarray(hg[k]), np.asarray(ho[k])), k
@@ -498,7 +472,7 @@ def test_multi_root_parity(roots, rounds, churn):
     slots, pt:76-84, :599-631; message ids past the 64 message slots): the
     engine equals the oracle, with 4 roots (no overflow), under churn, and
     with 6 roots (full root slots, counted as overflow identically)."""
-    (gs, gst, _), (os_, ost, _) = _both(S.multi_root, roots=roots, rounds=rounds, churn=churn)
+    (gs, gst, _), (os_, ost, _) = _both(P.PARITY[f"multi_root_{roots}_{rounds}"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
     if roots <= 4 and not churn:
@@ -510,7 +484,7 @@ def test_multi_root_shard_invariance():
     def g3(cfg):
         cfg.n_shards = 3
         return _gpu(cfg)
-    (gs, gst, _), (os_, ost, _) = S.multi_root(g3, roots=4, rounds=120), S.multi_root(Oracle, roots=4, rounds=120)
+    (gs, gst, _), (os_, ost, _) = P.PARITY["multi_root_120"](g3), P.PARITY["multi_root_120"](Oracle)
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
@@ -560,7 +534,7 @@ def test_msg_slots_and_strict_gpu():
     the four root slots -- counted identically to the oracle by default, a
     failed step (PSIM_ECAPACITY) with strict = 1."""
     from partisan_amd.sim import SimError
-    (gs, gst, _), (os_, ost, _) = _both(S.multi_root, n=512, roots=6, rounds=60)
+    (gs, gst, _), (os_, ost, _) = _both(P.PARITY["multi_root_512_6"])
     S.compare_stats(gst, ost)
     for a, b in zip(gs.msg_slots(), os_.msg_slots()):
         assert np.array_equal(a, b)
@@ -573,7 +547,7 @@ def test_heartbeat_parity():
     64 nodes beating every 10 rounds overflow the 4 root slots; GPU and
     oracle count the same overflows (strict = 0) and both fail the step with
     strict = 1 (the test above covers the GPU's error)."""
-    (gs, gst), (os_, ost) = _both(S.heartbeat)
+    (gs, gst), (os_, ost) = _both(P.PARITY["heartbeat"])
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
     assert int(ost["overflow_by"][:, 2].sum()) > 0
@@ -617,7 +591,7 @@ def test_xbot_parity(period):
     the stopped pids' EXITs one round later, the JOIN / FORWARD_JOIN /
     NEIGHBOR_REQUEST variants -- GPU == oracle (period 10: a busier overlay
     whose id-map and connection-table overflows are counted identically)."""
-    (gs, gst), (os_, ost) = _both(S.churn_partition, n=2048, manager=2, xbot_period=period)
+    (gs, gst), (os_, ost) = _both(P.PARITY[f"xbot_{period}"])
     assert ost["emitted"][:, 16:22].sum() > 1000
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
@@ -627,22 +601,17 @@ def test_xbot_shard_invariance():
     def gpu_sharded(cfg):
         cfg.n_shards = 3
         return _gpu(cfg)
-    gs, gst = S.churn_partition(gpu_sharded, n=2048, manager=2, xbot_period=20)
-    os_, ost = S.churn_partition(Oracle, n=2048, manager=2, xbot_period=20)
+    gs, gst = P.PARITY["xbot_20"](gpu_sharded)
+    os_, ost = P.PARITY["xbot_20"](Oracle)
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
 
 
 def test_xbot_64k_parity():
-    (gs, gst), (os_, ost) = _both(S.doubling, 1 << 16, 31, 70, bcast_period=10, bcast_first=30,
-                                  manager=2, xbot_period=12)
+    (gs, gst), (os_, ost) = _both(P.PARITY["xbot_64k"])
     assert ost["emitted"][:, 16:22].sum() > 10000
     S.compare_stats(gst, ost)
     S.compare_nodes(gs.nodes(), os_.nodes())
-
-
-def _both_tab(fn, seed, *a, **kw):
-    return fn(S.with_buckets(_gpu, seed), *a, **kw), fn(S.with_buckets(Oracle, seed), *a, **kw)
 
 
 @pytest.mark.parametrize("case", ["config_a", "churn_partition", "doubling_64k", "xbot", "scamp_v1"])
@@ -651,20 +620,8 @@ def test_bucket_table_parity(case):
     (psim_set_bucket_table, what an in-BEAM harness export of
     erlang:phash(NodeSpec, 16) supplies) -- GPU == oracle bit for bit, and
     the views follow the table."""
-    if case == "config_a":
-        (gs, gst), (os_, ost) = _both_tab(S.config_a, 11)
-    elif case == "churn_partition":
-        (gs, gst), (os_, ost) = _both_tab(S.churn_partition, 12, n=2048)
-    elif case == "doubling_64k":
-        def run(make):
-            sim, st = S.doubling(make, 1 << 16, 21, 60)
-            sim.broadcast(0, 5)
-            return sim, np.concatenate([st, sim.step(30)])
-        (gs, gst), (os_, ost) = _both_tab(run, 13)
-    elif case == "xbot":
-        (gs, gst), (os_, ost) = _both_tab(S.xbot_churn, 14, n=1024, rounds=100)
-    else:
-        (gs, gst), (os_, ost) = _both_tab(S.pl_doubling, 15, 2048, 5, 60, 1, crash_at=30, part_at=40)
+    (gs, gst), (os_, ost) = _both(P.PARITY["buckets_" + case])
+    if case == "scamp_v1":
         S.compare_stats(gst, ost)
         S.compare_strategy(gs, os_)
         return

@@ -8,6 +8,7 @@ strategy row at the end.  The oracle's set order is pinned against a
 bucket-level model of stdlib sets.erl by tests/test_sets_v1.py."""
 import pytest
 
+import _parity_registry as P
 import _scenarios as S
 from _oracle import Oracle
 
@@ -39,8 +40,10 @@ def _loop(world):
                                               (_loop(2), 180, 20)],
                          ids=["gpu-180", "gpu-200", "3-shards", "loopback-2"])
 def test_scamp_v1_large_view_parity(make, n, per_round):
-    o, ost, otr = S.pl_v1_large_view(S.with_phash(Oracle, 3), n=n, per_round=per_round)
-    g, gst, gtr = S.pl_v1_large_view(S.with_phash(make, 3), n=n, per_round=per_round)
+    run = P.sets_v1(f"sets_v1_{n}")              # (the registry's entry: S.pl_v1_large_view under a phash table)
+    assert P.SETS_V1[f"sets_v1_{n}"] == (n, per_round)
+    o, ost, otr = run(Oracle)
+    g, gst, gtr = run(make)
     assert max(x[0] for x in otr) > 100 and max(x[1] for x in otr) >= 22     # past 80: expanded
     assert otr[-1][1] <= 17 and int(ost["overflow"].sum()) == 0              # contracted again
     S.compare_stats(gst, ost)
