@@ -696,6 +696,61 @@ int psim_get_resilience(psim_handle *h, const psim_failure_case *cases, size_t n
 int psim_snapshot(psim_handle *h, void *buf, size_t cap, size_t *need);
 int psim_restore(psim_handle *h, const void *buf, size_t size);
 
+/* Message trace: the records sent to or by watched nodes, captured on the
+ * device ("Message trace") -- the engine's side of the
+ * message stream partisan_trace_orchestrator records through interposition.
+ * Read-only and off by default: an unarmed handle launches and allocates
+ * nothing for it, and the rounds stepped with a watch armed are those of a run
+ * without it (psim_step then runs single rounds, as under PSIM_NO_BATCH).
+ *   While a watch is armed, after every round r stepped (r =
+ * psim_round_stats.round) the engine captures the records sent in it -- the
+ * inbox round r + 1 will read: every successful send, whether or not the
+ * recipient is up to handle it.  A record is kept if bit (its type) of
+ * type_mask is set (psim_msg_type / psim_pl_msg_type) and its dst is watched
+ * with PSIM_TRACE_TO in dir, or its src is watched with PSIM_TRACE_FROM.
+ *   A record is 16 words in psim_wire_encode's layout (dst, src, type |
+ * ttl << 8 | nex << 16, seq, a0..a3, ex[0..8)); rounds[i] is the r of record
+ * i.  Records come in ascending (round, dst, src, seq) order -- the inbox's
+ * canonical order, round by round -- whatever the shard count.  Under the
+ * full strategy the words past the first four of a STATE or GOSSIP record are
+ * references into a shard-local arena, copied as they are: opaque.  (Word 7
+ * of a pluggable handle's other records, an arena slot inside the engine and
+ * no part of the message, comes out 0, as from psim_get_outbound.)
+ * psim_trace_watch  arms a watch on the n ids of nodes (a set: a repeated id
+ *     is legal; nodes == NULL with n == 0: every node), replacing the one
+ *     before it with its buffered records and lost count; it takes effect with
+ *     the next round stepped.  capacity: the records kept between two reads --
+ *     the first `capacity` matches in the order above, whatever the number of
+ *     virtual shards; every later match counts in `lost`.  Errors, in this
+ *     order: PSIM_EINVAL for a null h, null nodes with n > 0, dir 0 or above
+ *     3, type_mask 0 or with a bit at or above PSIM_MSG_NTYPES, capacity 0;
+ *     PSIM_EUNSUPPORTED for a host-exchange handle (psim_get_outbound is its
+ *     view); PSIM_ERANGE for an id >= n_nodes; PSIM_ENOMEM when the buffers
+ *     (64 + 4 bytes a record and n_nodes / 8 bytes, per shard) cannot be
+ *     allocated: the handle stays usable and the old watch as it was.
+ * psim_trace_read   *n = the records kept, *lost (may be NULL) = the matches
+ *     beyond them.  With recs == NULL or cap (in records) < *n that is all;
+ *     otherwise every record is copied out (rounds must be non-NULL), the
+ *     buffer emptied and lost zeroed, so the whole capacity is free again.
+ *     PSIM_EINVAL for a null h or n, or rounds NULL with recs given;
+ *     PSIM_ESTATE with no watch armed.  Works on a handle a failed psim_step
+ *     left unusable.
+ * psim_trace_clear  disarms the watch and frees its buffers; a no-op on an
+ *     unarmed handle.
+ * A rank handle traces the records whose dst it owns, with its own capacity,
+ * and makes no collective (as psim_get_nodes answers for owned ids); since an
+ * armed handle steps round by round, every rank arms and clears its watch
+ * before the same psim_step.  psim_snapshot does not include the trace and
+ * psim_restore leaves the watch and the buffered records alone.  No Erlang
+ * binding yet. */
+#define PSIM_TRACE_TO   1u   /* a record whose dst is watched */
+#define PSIM_TRACE_FROM 2u   /* a record whose src is watched */
+int psim_trace_watch(psim_handle *h, const uint32_t *nodes, size_t n, uint32_t dir,
+                     uint32_t type_mask, size_t capacity);
+int psim_trace_read(psim_handle *h, uint32_t *recs, uint32_t *rounds, size_t cap,
+                    size_t *n, uint64_t *lost);
+int psim_trace_clear(psim_handle *h);
+
 /* The live Plumtree message slots (plumtree_backend's ETS set keyed by
  * message id, :140-167): ids[k] = the message id owning slot k (PSIM_NONE =
  * free) and roots[k] its root (node_spec identity, | PSIM_MAP_BIT), for

@@ -30,6 +30,7 @@ MSG_TYPES = [
 ]
 PL_MSG_TYPES = ["HELLO", "STATE", "GOSSIP", "FWD_SUB", "PING", "KEEP_SUB", "REMOVE_SUB", "BOOT_REMOVE"]
 OMIT_SEND, OMIT_RECEIVE = 0, 1
+PSIM_TRACE_TO, PSIM_TRACE_FROM = 1, 2
 HV_TYPES = list(range(0, 9))
 PT_TYPES = list(range(9, 14))
 XBOT_TYPES = list(range(16, 22))
@@ -246,6 +247,10 @@ GPU_ONLY = {
     "get_tree_metrics": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(PsimTreeMetrics)]),
     "get_resilience": (C.c_int, [_H, C.POINTER(PsimFailureCase), C.c_size_t, C.c_uint64, C.c_uint32,
                                  C.POINTER(PsimResilience)]),
+    # the message trace (no oracle twin: the tests filter Oracle.inbox())
+    "trace_watch": (C.c_int, [_H, _P32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_size_t]),
+    "trace_read": (C.c_int, [_H, _P32, _P32, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "trace_clear": (C.c_int, [_H]),
 }
 # the host boundary (host-exchange handles: sim.HostSim, wire.check)
 HOST_BOUNDARY = {

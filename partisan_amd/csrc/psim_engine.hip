@@ -2986,6 +2986,109 @@ __global__ void __launch_bounds__(BLK) k_tm_final(const uint32_t* __restrict__ i
         if (sh[j]) atomicAdd(&tf[j], sh[j]);
 }
 
+// ------------------------------------------------------- message trace --
+// psim_trace_watch ("Message trace"): after a round, the
+// records of the shard's next inbox that pass the watch, copied in inbox order
+// to the shard's trace buffer.  Two launches: k_trace_count leaves every
+// block's match count and the ballots of its 64-record groups, k_trace_copy
+// ranks the matches from those and copies them.  A block takes `span`
+// consecutive records, a multiple of 64, so a wave's 64 lanes always hold one
+// aligned group; at most TR_BLK blocks, so that k_trace_copy sums the counts of
+// the blocks before its own with one load per thread: span is TR_SPAN up to
+// TR_BLK * TR_SPAN records (2 M) and grows past that.  No atomics: the rank of
+// a record follows from its position alone.
+constexpr uint32_t TR_BLK = 1024;
+constexpr uint32_t TR_SPAN = 2048;
+constexpr uint32_t TR_WAVES = TR_BLK / 64;
+
+// bits == nullptr: every node is watched
+struct TraceWatch {
+    const uint32_t* bits;    // n_nodes bits, by global id
+    uint32_t n_nodes, dir, type_mask;
+};
+
+DEV bool trace_watched(const TraceWatch& w, uint32_t id) {
+    return !w.bits || (id < w.n_nodes && ((w.bits[id >> 5] >> (id & 31u)) & 1u));
+}
+
+__global__ void __launch_bounds__(TR_BLK) k_trace_count(const Msg* __restrict__ inbox, uint32_t m, uint32_t span,
+                                                        TraceWatch w, uint32_t* __restrict__ cnt,
+                                                        unsigned long long* __restrict__ ballots) {
+    __shared__ uint32_t wc[TR_WAVES];
+    const uint64_t base = (uint64_t)blockIdx.x * span;
+    uint32_t c = 0;
+    for (uint32_t off = threadIdx.x; off < span; off += TR_BLK) {   // (uniform per wave: span is a multiple of 64)
+        const uint64_t i = base + off;
+        bool hit = false;
+        if (i < m) {
+            const uint4 hd = *reinterpret_cast<const uint4*>(inbox + i);   // dst, src, type word, seq
+            const uint32_t t = hd.z & 0xFFu;
+            hit = t < 32u && ((w.type_mask >> t) & 1u) &&
+                  (((w.dir & PSIM_TRACE_TO) && trace_watched(w, hd.x)) ||
+                   ((w.dir & PSIM_TRACE_FROM) && trace_watched(w, hd.y)));
+        }
+        const uint64_t b = ballot(hit);
+        if (lane_id() == 0) ballots[i >> 6] = b;
+        c += popc(b);
+    }
+    if (lane_id() == 0) wc[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t k = 0; k < TR_WAVES; k++) t += wc[k];
+        cnt[blockIdx.x] = t;
+    }
+}
+
+// tot_in[0]: the shard's matches before this round (its stored records: the
+// first `cap` of them); the last block leaves tot_in[0] + this round's in
+// tot_out[0] -- two words the host swaps each round, so no block reads the
+// word another writes.  Four lanes copy one record, 16 B each.
+__global__ void __launch_bounds__(TR_BLK) k_trace_copy(const Msg* __restrict__ inbox, uint32_t span,
+                                                       const uint32_t* __restrict__ cnt,
+                                                       const unsigned long long* __restrict__ ballots,
+                                                       const unsigned long long* __restrict__ tot_in,
+                                                       unsigned long long* __restrict__ tot_out,
+                                                       Msg* __restrict__ out, uint32_t* __restrict__ rounds,
+                                                       unsigned long long cap, uint32_t round) {
+    __shared__ uint32_t wsum[TR_WAVES], wc[TR_WAVES];
+    __shared__ uint8_t sel[TR_WAVES][64];
+    const uint32_t l = lane_id(), wv = threadIdx.x >> 6;
+    // the matches of the blocks before this one (gridDim.x <= TR_BLK)
+    const uint32_t mine = sh_wave_sum(threadIdx.x < blockIdx.x ? cnt[threadIdx.x] : 0u);
+    if (l == 0) wsum[wv] = mine;
+    __syncthreads();
+    unsigned long long rank0 = tot_in[0];
+    for (uint32_t k = 0; k < TR_WAVES; k++) rank0 += wsum[k];
+    const uint64_t base = (uint64_t)blockIdx.x * span;
+    for (uint32_t p0 = 0; p0 < span; p0 += TR_BLK) {                // (uniform per block: the barriers below)
+        const uint32_t off = p0 + wv * 64u;
+        const uint64_t g0 = base + off;                             // the wave's group (none past the span)
+        const uint64_t b = off < span ? ballots[g0 >> 6] : 0ull;
+        const uint32_t nb = popc(b);
+        if ((b >> l) & 1u) sel[wv][popc(b & ((1ull << l) - 1ull))] = (uint8_t)l;
+        if (l == 0) wc[wv] = nb;
+        __syncthreads();
+        unsigned long long r = rank0;
+        uint32_t pass = 0;
+        for (uint32_t k = 0; k < TR_WAVES; k++) {
+            r += k < wv ? wc[k] : 0u;
+            pass += wc[k];
+        }
+        for (uint32_t q = l >> 2; q < nb; q += 16u) {               // the q-th match of the group, piece l & 3
+            const unsigned long long at = r + q;
+            if (at < cap) {
+                const uint4* sp = reinterpret_cast<const uint4*>(inbox + g0 + sel[wv][q]);
+                reinterpret_cast<uint4*>(out + at)[l & 3u] = sp[l & 3u];
+                if ((l & 3u) == 0) rounds[at] = round;
+            }
+        }
+        rank0 += pass;
+        __syncthreads();
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) tot_out[0] = rank0;
+}
+
 // ------------------------------------------------------------- buffers --
 template <typename T>
 struct DBuf {
@@ -3071,9 +3174,10 @@ struct TmpBuf : DBuf<T> {
 };
 
 enum Kern { KT_EVENTS, KT_PREPARE, KT_CONSUME, KT_SCAN, KT_COMPACT, KT_SORT, KT_EXCHANGE, KT_GATHER,
-            KT_STATS, KT_HOST_EXPORT, KT_HOST_IMPORT, KT_PACK, KT_N };
+            KT_STATS, KT_HOST_EXPORT, KT_HOST_IMPORT, KT_PACK, KT_TRACE_COUNT, KT_TRACE_COPY, KT_N };
 const char* kKernName[KT_N] = {"events", "prepare", "consume", "scan", "compact", "sort",
-                               "exchange", "gather", "stats", "k_host_export", "k_host_import", "pay_pack"};
+                               "exchange", "gather", "stats", "k_host_export", "k_host_import", "pay_pack",
+                               "k_trace_count", "k_trace_copy"};
 
 inline uint32_t grid_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + BLK - 1) / BLK); }
 
@@ -3209,6 +3313,16 @@ struct Shard {
     uint32_t xcap_h = 0, xcap_t = 0;
     uint32_t xbatch = 1;
     uint64_t trace_tmax = 0, trace_mmax = 0;   // PSIM_TRACE_BOUND's high-water marks
+    // the message trace (psim_trace_watch; none of it allocated on an unarmed
+    // handle): the watch bitmap (global ids; none when every node is
+    // watched), the kept records with their rounds, the shard's matches since
+    // the last read (two words, swapped every captured round: tr_cur names
+    // the current one; the first `capacity` of them are kept), and a round's
+    // scratch (block counts, group ballots)
+    DBuf<uint32_t> tr_bits, tr_round, tr_cnt;
+    DBuf<Msg> tr_rec;
+    DBuf<unsigned long long> tr_tot, tr_ballot;
+    int tr_cur = 0;
 };
 
 // the events a handle holds for its next round (psim_handle's pend_* members)
@@ -3295,6 +3409,12 @@ struct psim_handle {
     // of k_bucket_hist + k_bucket_offsets + k_bucket_scatter
     // (PSIM_ROUTE_FUSED=0: the four passes, for A/B; reroutes take them too)
     bool route_fused = true;
+    // the message trace: a watch is armed (psim_step then runs single rounds
+    // and captures after each), every node watched, PSIM_TRACE_* directions,
+    // the type mask, records kept between two reads (per shard, and in all)
+    bool trace_on = false, trace_all = false;
+    uint32_t trace_dir = 0, trace_mask = 0;
+    size_t trace_cap = 0;
 };
 
 namespace {
@@ -4773,6 +4893,43 @@ int host_absorb(psim_handle* h, size_t nb, uint64_t* st) {
     return PSIM_OK;
 }
 
+// The message trace's capture of round `round`, just stepped (psim_step, an
+// armed handle): per shard two launches on its stream over the next round's
+// inbox, inbox[0 .. m_in) -- none where it is empty.  On the shard's stream
+// the capture stands before the next round's kernels, the only ones that
+// overwrite the inbox.
+int trace_capture(psim_handle* h, uint32_t round) {
+    for (Shard* s : h->shards) {
+        const uint32_t m = s->m_in;
+        if (!m) continue;
+        uint32_t span = TR_SPAN;
+        if (m > TR_BLK * TR_SPAN) span = (uint32_t)((((uint64_t)m + TR_BLK - 1) / TR_BLK + 63u) / 64u * 64u);
+        const uint32_t grid = (uint32_t)(((uint64_t)m + span - 1) / span);   // <= TR_BLK
+        TRY(s->tr_cnt.ensure(grid));
+        TRY(s->tr_ballot.ensure((size_t)grid * (span / 64u)));
+        const TraceWatch w{h->trace_all ? nullptr : s->tr_bits.p, h->N, h->trace_dir, h->trace_mask};
+        {
+            KTimer t(h, s, KT_TRACE_COUNT);
+            k_trace_count<<<grid, TR_BLK, 0, s->stream>>>(s->inbox.p, m, span, w, s->tr_cnt.p, s->tr_ballot.p);
+        }
+        {
+            KTimer t(h, s, KT_TRACE_COPY);
+            k_trace_copy<<<grid, TR_BLK, 0, s->stream>>>(s->inbox.p, span, s->tr_cnt.p, s->tr_ballot.p,
+                                                         s->tr_tot.p + s->tr_cur, s->tr_tot.p + (s->tr_cur ^ 1),
+                                                         s->tr_rec.p, s->tr_round.p,
+                                                         (unsigned long long)h->trace_cap, round);
+        }
+        HIP_TRY(hipGetLastError());
+        s->tr_cur ^= 1;
+    }
+    if (h->phase_timers)                        // (the next round's front drops timers not read yet)
+        for (Shard* s : h->shards) {
+            TRY(stream_wait(s));
+            flush_timers(h, s);
+        }
+    return PSIM_OK;
+}
+
 // Whether psim_step may run its rounds as batches (run_batch): one RCCL-free
 // HyParView shard past its first round, no diagnostic mode that reads the
 // device between kernels, no strict mode (it stops at the overflowing round)
@@ -4780,8 +4937,10 @@ bool batchable(psim_handle* h) {
     static const bool trace = getenv("PSIM_TRACE_RELAY") != nullptr;
     static const bool off = getenv("PSIM_NO_BATCH") != nullptr || getenv("PSIM_TEST_FAIL_ROUND") != nullptr;
     static const bool off_ranked = getenv("PSIM_NO_RANK_BATCH") != nullptr;
+    // (an armed message trace captures after every round: run_round knows
+    // each round's inbox on the host, a batch does not)
     if (off || trace || h->phase_timers || h->cfg.strict || h->cfg.manager == PSIM_MANAGER_PLUGGABLE ||
-        !h->pend_lv_a.empty())
+        !h->pend_lv_a.empty() || h->trace_on)
         return false;
     Shard* s = h->shards[0];
     // a rank batches once an exact round has set the exchange capacities.
@@ -5190,6 +5349,13 @@ int shard_alloc(psim_handle* h, Shard* s) {
     return PSIM_OK;
 }
 
+// a shard's message-trace buffers (psim_trace_clear, a replaced watch, shard_free)
+void trace_release(Shard* s) {
+    s->tr_bits.release(); s->tr_round.release(); s->tr_cnt.release(); s->tr_rec.release();
+    s->tr_tot.release(); s->tr_ballot.release();
+    s->tr_cur = 0;
+}
+
 void shard_free(Shard* s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     s->flags.release(); s->part.release(); s->upart.release(); s->lite_cm.release(); s->hdr.release(); s->crash_bits.release(); s->btab.release();
@@ -5223,6 +5389,7 @@ void shard_free(Shard* s) {
     s->sview.release(); s->sinv.release(); s->fbits.release(); s->pay[0].release(); s->pay[1].release();
     s->pay_top.release();
     s->pbits.release(); s->prank.release(); s->plist.release(); s->paysend.release(); s->pay_imp.release(); s->pcnt_d.release();
+    trace_release(s);
     if (s->ev_live)
         for (int k = 0; k < Shard::MAXT; k++) {
             (void)hipEventDestroy(s->ev[k][0]);
@@ -5671,6 +5838,8 @@ int psim_step(psim_handle* h, uint32_t n_rounds, psim_round_stats* stats) {
         if (rc) { h->failed = true; return rc; }
         for (Shard* s : h->shards)
             if ((rc = grow_outx(s))) { h->failed = true; return rc; }
+        // (the round is whole: a capture that fails ends the step, the handle stays usable)
+        if (h->trace_on && (rc = trace_capture(h, (uint32_t)r))) return rc;
         if (stats) fill_stats(st, r, &stats[i]);
         if (h->cfg.strict && st[ST_OVF]) return PSIM_ECAPACITY;   // cfg.strict: fail loudly
         i++;
@@ -6816,6 +6985,139 @@ int psim_restore(psim_handle* h, const void* buf, size_t size) {
     h->pend_join_mark.assign(h->pend_join_mark.size(), 0);
     h->pend_part_set = h->pend_part_clear = false;
     h->pend_b_root.clear(); h->pend_b_msg.clear();
+    return PSIM_OK;
+}
+
+// ---- the message trace ("Message trace")
+int psim_trace_watch(psim_handle* h, const uint32_t* nodes, size_t n, uint32_t dir, uint32_t type_mask,
+                     size_t capacity) {
+    if (!h || (!nodes && n) || dir == 0 || dir > (PSIM_TRACE_TO | PSIM_TRACE_FROM) || type_mask == 0 ||
+        (type_mask >> PSIM_MSG_NTYPES) != 0 || capacity == 0)
+        return PSIM_EINVAL;
+    if (h->hosted) return PSIM_EUNSUPPORTED;          // (psim_get_outbound shows its records)
+    for (size_t i = 0; i < n; i++)
+        if (nodes[i] >= h->N) return PSIM_ERANGE;
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    const bool all = !nodes;
+    std::vector<uint32_t> bits;
+    if (!all) {
+        bits.assign((h->N + 31) / 32, 0);
+        for (size_t i = 0; i < n; i++) bits[nodes[i] >> 5] |= 1u << (nodes[i] & 31u);
+    }
+    // the new buffers first: a failed allocation leaves the old watch as it was
+    struct Fresh {
+        DBuf<uint32_t> bits, round;
+        DBuf<Msg> rec;
+        DBuf<unsigned long long> tot;
+        void release() { bits.release(); round.release(); rec.release(); tot.release(); }
+    };
+    auto raw = [](auto& b, size_t want) -> int {      // (not cleared: the kernels write what is read)
+        if (hipMalloc(&b.p, want * sizeof(*b.p)) != hipSuccess) {
+            (void)hipGetLastError();
+            b.p = nullptr;
+            return PSIM_ENOMEM;
+        }
+        b.n = want;
+        return PSIM_OK;
+    };
+    std::vector<Fresh> fresh(h->shards.size());
+    int rc = capacity > SIZE_MAX / sizeof(Msg) ? PSIM_ENOMEM : PSIM_OK;
+    for (size_t k = 0; k < fresh.size() && !rc; k++) {
+        Shard* s = h->shards[k];
+        if (!all) rc = raw(fresh[k].bits, bits.size());
+        if (!rc) rc = raw(fresh[k].rec, capacity);
+        if (!rc) rc = raw(fresh[k].round, capacity);
+        if (!rc) rc = fresh[k].tot.alloc_on(2, s->stream);
+        if (!rc && !all &&
+            hipMemcpyAsync(fresh[k].bits.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess)
+            rc = PSIM_EDEVICE;
+        if (!rc && hipStreamSynchronize(s->stream) != hipSuccess) rc = PSIM_EDEVICE;   // (bits: a local vector)
+    }
+    if (rc) {
+        for (Fresh& f : fresh) f.release();
+        return rc;
+    }
+    for (size_t k = 0; k < fresh.size(); k++) {
+        Shard* s = h->shards[k];
+        trace_release(s);                             // (the stream is idle: synchronised above)
+        s->tr_bits = fresh[k].bits; s->tr_round = fresh[k].round; s->tr_rec = fresh[k].rec; s->tr_tot = fresh[k].tot;
+    }
+    h->trace_on = true; h->trace_all = all;
+    h->trace_dir = dir; h->trace_mask = type_mask; h->trace_cap = capacity;
+    return PSIM_OK;
+}
+
+int psim_trace_read(psim_handle* h, uint32_t* recs, uint32_t* rounds, size_t cap, size_t* n, uint64_t* lost) {
+    if (!h || !n || (recs && !rounds)) return PSIM_EINVAL;
+    if (!h->trace_on) return PSIM_ESTATE;
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    // per shard: its matches since the last read, the first trace_cap of them stored
+    const size_t S = h->shards.size();
+    std::vector<uint64_t> stored(S);
+    uint64_t matched = 0, have = 0;
+    for (size_t k = 0; k < S; k++) {
+        Shard* s = h->shards[k];
+        unsigned long long t = 0;
+        HIP_TRY(hipMemcpyAsync(&t, s->tr_tot.p + s->tr_cur, 8, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        stored[k] = std::min<uint64_t>(t, h->trace_cap);
+        matched += t;
+        have += stored[k];
+    }
+    // the first trace_cap matches of all shards in (round, dst, src, seq)
+    // order: those of one shard are a prefix of its buffer
+    const uint64_t kept = std::min<uint64_t>(have, h->trace_cap);
+    *n = (size_t)kept;
+    if (lost) *lost = matched - kept;
+    if (!recs || cap < kept) return PSIM_OK;
+    std::vector<Msg> all((size_t)have);
+    std::vector<uint32_t> rd((size_t)have);
+    size_t at = 0;
+    for (size_t k = 0; k < S; k++) {
+        Shard* s = h->shards[k];
+        if (!stored[k]) continue;
+        HIP_TRY(hipMemcpy(all.data() + at, s->tr_rec.p, stored[k] * sizeof(Msg), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rd.data() + at, s->tr_round.p, stored[k] * 4, hipMemcpyDeviceToHost));
+        at += stored[k];
+    }
+    std::vector<size_t> ord(all.size());
+    for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+    auto before = [&](size_t a, size_t b) {
+        if (rd[a] != rd[b]) return rd[a] < rd[b];
+        const Msg &x = all[a], &y = all[b];
+        if (x.dst != y.dst) return x.dst < y.dst;
+        if (x.src != y.src) return x.src < y.src;
+        return x.seq < y.seq;
+    };
+    // (one shard's buffer is in this order already: the inbox's, round by round)
+    if (!std::is_sorted(ord.begin(), ord.end(), before)) std::stable_sort(ord.begin(), ord.end(), before);
+    // (a pluggable handle's word 7 is a payload-arena slot, no part of the
+    // message: 0, as k_host_export leaves it -- but for the full strategy's
+    // STATE and GOSSIP records, whose payload words stay the references they are)
+    const bool pl = h->cfg.manager == PSIM_MANAGER_PLUGGABLE;
+    for (size_t i = 0; i < kept; i++) {
+        uint32_t* o = recs + i * 16;
+        memcpy(o, &all[ord[i]], sizeof(Msg));
+        const uint32_t t = o[2] & 0xFFu;
+        if (pl && !(h->fw && (t == PSIM_PL_STATE || t == PSIM_PL_GOSSIP))) o[7] = 0;
+        rounds[i] = rd[ord[i]];
+    }
+    for (Shard* s : h->shards) {                      // the buffers are free again
+        HIP_TRY(hipMemsetAsync(s->tr_tot.p, 0, 2 * sizeof(unsigned long long), s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    return PSIM_OK;
+}
+
+int psim_trace_clear(psim_handle* h) {
+    if (!h) return PSIM_EINVAL;
+    if (!h->trace_on) return PSIM_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
+    for (Shard* s : h->shards) {
+        (void)hipStreamSynchronize(s->stream);
+        trace_release(s);
+    }
+    h->trace_on = false;
     return PSIM_OK;
 }
 

@@ -474,6 +474,42 @@ class Simulator(_Driver):
             out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
         return out
 
+    # ---- the message trace (psim_trace_watch / psim_trace_read / psim_trace_clear)
+    def trace_watch(self, nodes=None, to=True, frm=True, types=None, capacity=1 << 20):
+        """Arm a watch: from the next round on, the records sent to (`to`) or
+        by (`frm`) the ids in `nodes` (None: every node) are kept, up to
+        `capacity` between two reads.  `types`: an iterable of message type
+        numbers (None: all).  Replaces an earlier watch and drops its records."""
+        mask = (1 << _abi.NTYPES) - 1
+        if types is not None:
+            mask = 0
+            for t in types:
+                mask |= 1 << int(t)
+        d = (_abi.PSIM_TRACE_TO if to else 0) | (_abi.PSIM_TRACE_FROM if frm else 0)
+        if nodes is None:
+            ptr, n = None, 0
+        else:
+            ids = np.ascontiguousarray(nodes, np.uint32).reshape(-1)
+            ptr, n = _abi.u32p(ids), ids.size
+        self._check(self._extra["trace_watch"](self._h, ptr, n, d, mask & 0xFFFFFFFF, capacity), "trace_watch")
+
+    def trace_read(self):
+        """(recs[n, 16] uint32, rounds[n] uint32, lost): the records kept since
+        the last read, in (round, dst, src, seq) order, each in the wire
+        codec's layout, and the number of matches past the capacity.  Empties
+        the buffer."""
+        n, lost = C.c_size_t(), C.c_uint64()
+        self._check(self._extra["trace_read"](self._h, None, None, 0, C.byref(n), C.byref(lost)), "trace_read")
+        recs = np.zeros((n.value, 16), np.uint32)
+        rounds = np.zeros(n.value, np.uint32)
+        self._check(self._extra["trace_read"](self._h, _abi.u32p(recs), _abi.u32p(rounds), n.value, C.byref(n),
+                                              C.byref(lost)), "trace_read")
+        return recs, rounds, lost.value
+
+    def trace_clear(self):
+        """Disarm the watch and free its buffers (a no-op without one)."""
+        self._check(self._extra["trace_clear"](self._h), "trace_clear")
+
     # (k_node_prep: the quiet lazy ticks it counts without running the node)
     KERNELS = ("k_relay", "k_shuf", "k_lite_half", "k_consume", "k_ptl", "k_pt", "k_node_prep")
 
