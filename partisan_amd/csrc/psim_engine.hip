@@ -1,6 +1,7 @@
 // psim_engine.hip -- device memory, event kernels, the message route
 // (K-route), the cross-shard exchange and the C ABI of
-// include/partisan_gpu_sim.h.
+// include/partisan_gpu_sim.h, but for the read-only analyses of the overlay
+// (psim_metrics.hip).  The handle's and the shards' state: psim_host.h.
 //
 // The global id space [0, N) is cut into G contiguous shards.  A process owns
 // `n_shards` of them (virtual shards on its device, exchanged by device
@@ -39,17 +40,14 @@
 #include <set>
 #include <vector>
 
-#include "psim_comm.h"
+#include "psim_host.h"
 #include "psim_payload.h"
-#include "psim_device.h"
-#include "psim_kernels.h"
 #include "psim_wave.h"
 
 using namespace psim;
 
 namespace {
 
-constexpr int BLK = 256;
 constexpr uint32_t PREP_BLK = 1024;   // k_desc blocks (at most PREP_BLK of them)
 #ifndef PSIM_PREP_NPT
 #define PSIM_PREP_NPT 4       // (2: step 0.620 -> 0.615 ms at 2^20 against 1 node a thread, profiles/r05/ab_log.txt r6m, r6n)
@@ -82,22 +80,6 @@ constexpr uint32_t STAT_OUT_X = NST + 2, STAT_OUT_R = NST + 5, STAT_OUT_N = NST 
 // slot j + 1 the stats and node-round span of round j of a batch (run_batch)
 constexpr uint32_t PIN_STRIDE = PIN_XRANK + 128;
 constexpr uint32_t BATCH_MAX = 64;
-
-#define HIP_TRY(x)                                                       \
-    do {                                                                 \
-        hipError_t e_ = (x);                                             \
-        if (e_ != hipSuccess) {                                          \
-            std::fprintf(stderr, "psim: %s failed: %s (%s:%d)\n", #x,    \
-                         hipGetErrorString(e_), __FILE__, __LINE__);     \
-            return PSIM_EDEVICE;                                         \
-        }                                                                \
-    } while (0)
-
-#define TRY(x)                   \
-    do {                         \
-        int rc_ = (x);           \
-        if (rc_) return rc_;     \
-    } while (0)
 
 // ------------------------------------------------------------ kernels --
 __global__ void k_crash(uint8_t* flags, uint32_t* crash_bits, const uint32_t* ids, uint32_t n) {
@@ -262,20 +244,13 @@ constexpr uint32_t RUN_LDS = 2048;
 constexpr uint32_t RB_STEP = PSIM_RB_STEP;
 constexpr uint32_t RB_WAVES = RB_STEP / 64;
 constexpr uint32_t RB_MAX_BLOCKS = 1024;   // blocks of the two passes over the sources
-// ... by default: one resident generation (two 1024-thread blocks a CU) --
-// 1024 blocks were two generations of latency-bound steps at 2^20 (step
-// 0.619 -> 0.615 ms, profiles/r05/ab_log.txt r6n)
-constexpr uint32_t RB_BLOCKS = 512;
+// (their default number RB_BLOCKS, and k_bucket_route's RR_REG: psim_host.h, with psim_handle's members)
 #ifndef PSIM_RR_THREADS
 #define PSIM_RR_THREADS 1024
 #endif
 // k_bucket_route block: 1024 threads keep 16 waves per CU on its one block
 // per bucket (512: route 36 -> 31 us a round at 2^20, profiles/r03 p26)
 constexpr uint32_t RR_THREADS = PSIM_RR_THREADS;
-#ifndef PSIM_RR_REG
-#define PSIM_RR_REG 6
-#endif
-constexpr uint32_t RR_REG = PSIM_RR_REG;   // k_bucket_route: pairs a thread holds in registers
 // bucket widths 2^11 .. 2^13 (route_group): k_bucket_route's LDS holds 4 W
 // words -- counts, bound sums, and W 64-bit BROADCAST masks whose 2 W words
 // then carry the block sort's RUN_LDS-word buffer and the long-run list (at
@@ -306,10 +281,7 @@ static_assert((1u << WSHIFT_MAX) * 16 <= 160 * 1024, "k_bucket_route: 16 W bytes
 // head's word 7 -- and turns a payload head's rank into PAY_IMPORT | the
 // row's index among every imported row -- and k_bucket_route gathers head +
 // tail (or zeros) into the 64-B inbox record, a long record's word 7 zeroed.
-struct __attribute__((aligned(16))) Wire {
-    uint4 q[2];
-};
-static_assert(sizeof(Wire) == 32, "a wire unit is half a record");
+// (struct Wire, a head or a tail: psim_host.h)
 __host__ __device__ __forceinline__ bool wire_long(uint32_t tt) { return ((tt >> 16) & 0xFFu) != 0u; }
 // the types whose word 7 names ORSet rows on a full-strategy handle (the payload exchange)
 __device__ __forceinline__ bool pay_type(uint32_t tt) {
@@ -532,9 +504,6 @@ __global__ void __launch_bounds__(RB_STEP) k_bucket_hist(RouteIn in, uint32_t ns
     __syncthreads();
     for (uint32_t j = threadIdx.x; j < nb; j += blockDim.x) hist[(size_t)j * gridDim.x + blockIdx.x] = hcnt[j];
 }
-
-template <typename T, uint32_t NT = BLK>
-__device__ T block_excl(T v, T* total);   // (the exclusive-scan section below)
 
 // Block b: row b of hist (nblk <= RB_MAX_BLOCKS counts, one a thread) scanned
 // into hoff, the row's sum into tot[b].  One launch where a scan over the
@@ -2004,988 +1973,6 @@ __global__ void __launch_bounds__(PREP_BLK) k_desc(const uint64_t* __restrict__ 
         desc_entry(a, a.n_local, carry, 0ull, DescIn{0, 0, 0, 0}, desc, obase, nact, tot, hout, cap, ctl);
 }
 
-// --------------------------------------------------------- overlay stats --
-// psim_get_histograms: per live node its view sizes, the in-degree links it
-// contributes (global id arrays, summed over shards / RCCL ranks) and the
-// tracked broadcast's delivery.  hist layout: 5 histograms of
-// PSIM_HIST_BINS, then n_up, delivered, last_round, active_links.
-enum { H_AIN = 0, H_PIN = 1, H_AOUT = 2, H_PFILL = 3, H_HOP = 4, H_NUP = 5 * PSIM_HIST_BINS,
-       H_DELIV, H_LAST, H_LINKS, H_N };
-
-__device__ __forceinline__ uint32_t hbin(uint32_t v) { return v < PSIM_HIST_BINS ? v : PSIM_HIST_BINS - 1; }
-
-__global__ void k_hist_out(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ act,
-                           const uint32_t* __restrict__ pas, const uint8_t* __restrict__ flags, uint32_t lo,
-                           uint32_t n, uint64_t tbit, uint32_t* indeg_a, uint32_t* indeg_p,
-                           unsigned long long* hist) {
-    __shared__ unsigned long long sh[H_N];
-    for (uint32_t j = threadIdx.x; j < H_N; j += blockDim.x) sh[j] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (flags[lo + i] & F_UP)) {
-        const Hdr& x = hdr[i];
-        const uint32_t me = lo + i;
-        uint32_t out = 0;
-        for (uint32_t k = 0; k < x.act_n; k++) {
-            const uint32_t p = act[(size_t)i * PSIM_ACTIVE_CAP + k];
-            if (p == me) continue;
-            out++;
-            if (flags[p] & F_UP) { atomicAdd(&indeg_a[p], 1u); atomicAdd(&sh[H_LINKS], 1ull); }
-        }
-        for (uint32_t k = 0; k < x.pas_n; k++) {
-            const uint32_t p = pas[(size_t)i * PSIM_PASSIVE_CAP + k];
-            if (p != me && (flags[p] & F_UP)) atomicAdd(&indeg_p[p], 1u);
-        }
-        atomicAdd(&sh[H_AOUT * PSIM_HIST_BINS + hbin(out)], 1ull);
-        atomicAdd(&sh[H_PFILL * PSIM_HIST_BINS + hbin(x.pas_n)], 1ull);
-        atomicAdd(&sh[H_NUP], 1ull);
-        if (tbit && ((((uint64_t)x.aux << 32) | x.have) & tbit)) {
-            atomicAdd(&sh[H_DELIV], 1ull);
-            atomicAdd(&sh[H_HOP * PSIM_HIST_BINS + hbin(x.trk_hop)], 1ull);
-            if (x.trk_round != PSIM_NONE) atomicMax(&sh[H_LAST], (unsigned long long)x.trk_round);
-        }
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < H_N; j += blockDim.x) {
-        if (!sh[j]) continue;
-        if (j == H_LAST) atomicMax(&hist[j], sh[j]);
-        else atomicAdd(&hist[j], sh[j]);
-    }
-}
-
-__global__ void k_hist_in(const uint32_t* __restrict__ indeg_a, const uint32_t* __restrict__ indeg_p,
-                          const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n, unsigned long long* hist) {
-    __shared__ unsigned long long sh[2 * PSIM_HIST_BINS];
-    for (uint32_t j = threadIdx.x; j < 2 * PSIM_HIST_BINS; j += blockDim.x) sh[j] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (flags[lo + i] & F_UP)) {
-        atomicAdd(&sh[hbin(indeg_a[lo + i])], 1ull);
-        atomicAdd(&sh[PSIM_HIST_BINS + hbin(indeg_p[lo + i])], 1ull);
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < 2 * PSIM_HIST_BINS; j += blockDim.x)
-        if (sh[j]) atomicAdd(&hist[H_AIN * PSIM_HIST_BINS + j], sh[j]);
-}
-
-// the whole overlay's active rows (gathered from every shard / RCCL rank into
-// gact / gan by global id): reverse-link test and label propagation over live
-// active links (min label, then pointer jumping)
-__global__ void k_pack_act(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ act, uint32_t n,
-                           uint32_t* gact, uint8_t* gan) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t k = hdr[i].act_n;
-    gan[i] = (uint8_t)k;
-    for (uint32_t j = 0; j < PSIM_ACTIVE_CAP; j++) gact[(size_t)i * PSIM_ACTIVE_CAP + j] = act[(size_t)i * PSIM_ACTIVE_CAP + j];
-}
-
-__global__ void k_hist_sym(const uint8_t* __restrict__ gan, const uint32_t* __restrict__ act,
-                           const uint8_t* __restrict__ flags, uint32_t n, unsigned long long* sym) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !(flags[i] & F_UP)) return;
-    uint32_t c = 0;
-    for (uint32_t k = 0; k < gan[i]; k++) {
-        const uint32_t p = act[(size_t)i * PSIM_ACTIVE_CAP + k];
-        if (p == i || p >= n || !(flags[p] & F_UP)) continue;
-        for (uint32_t q = 0; q < gan[p]; q++)
-            if (act[(size_t)p * PSIM_ACTIVE_CAP + q] == i) { c++; break; }
-    }
-    if (c) atomicAdd(sym, (unsigned long long)c);
-}
-
-__global__ void k_cc_init(const uint8_t* __restrict__ flags, uint32_t n, uint32_t* L) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) L[i] = (flags[i] & F_UP) ? i : PSIM_NONE;
-}
-
-// (node i's row: gan[i] ids at act + off[i] -- a CSR, the pluggable handles'
-// overlay -- or, off == nullptr, at act + i * PSIM_ACTIVE_CAP: HyParView's rows)
-__global__ void k_cc_hook(const uint32_t* __restrict__ off, const uint8_t* __restrict__ gan,
-                          const uint32_t* __restrict__ act, const uint8_t* __restrict__ flags, uint32_t n,
-                          uint32_t* L, uint32_t* changed) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !(flags[i] & F_UP)) return;
-    const uint32_t* row = act + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP);
-    for (uint32_t k = 0; k < gan[i]; k++) {
-        const uint32_t p = row[k];
-        if (p == i || p >= n || !(flags[p] & F_UP)) continue;
-        const uint32_t a = L[i], b = L[p];
-        if (a < b) { if (atomicMin(&L[p], a) > a) *changed = 1; }
-        else if (b < a) { if (atomicMin(&L[i], b) > b) *changed = 1; }
-    }
-}
-
-__global__ void k_cc_jump(uint32_t n, uint32_t* L) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || L[i] == PSIM_NONE) return;
-    uint32_t r = L[i];
-    while (L[r] != r) r = L[r];
-    L[i] = r;
-}
-
-__global__ void k_cc_count(const uint32_t* __restrict__ L, uint32_t n, uint32_t* size, unsigned long long* comps) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || L[i] == PSIM_NONE) return;
-    atomicAdd(&size[L[i]], 1u);
-    if (L[i] == i) atomicAdd(comps, 1ull);
-}
-
-__global__ void k_cc_max(const uint32_t* __restrict__ size, uint32_t n, unsigned long long* largest) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && size[i]) atomicMax(largest, (unsigned long long)size[i]);
-}
-
-// ------------------------------------------ overlay stats, pluggable --
-// psim_get_strategy_histograms.  A SCAMP row is PSIM_SVIEW_CAP ids with ~3 in
-// use, so the whole overlay is packed into a CSR instead of gathering rows:
-//   k_sh_rows (count)  a wave takes 64 local nodes and holds one view at a time
-//                      as two 64-lane registers (only the lanes below its
-//                      length load), marks
-//                      first occurrences, self and live targets, counts the
-//                      per-node statistics and writes the node's number of
-//                      distinct live targets != self (a byte, by global id)
-//   scan_excl          the counts (all-gathered across ranks) -> row offsets
-//   k_sh_rows (pack)   the same wave writes those targets at its offset
-//   k_sh_links / k_sh_in / k_sh_inv / k_cc_*   statistics over the CSR
-// sl layout (summed over ranks; SL_VMAX: max): three histograms, then scalars
-enum { SL_VFILL = 0, SL_IFILL = 1, SL_OUT = 2, SL_NUP = 3 * PSIM_HIST_BINS, SL_VSUM, SL_ISUM, SL_DANG, SL_SELF,
-       SL_DUP, SL_IVL, SL_IVC, SL_VMAX, SL_N };
-// sg layout (over the whole CSR, the same on every rank): the in-degree
-// histogram, then scalars
-enum { SG_LINKS = PSIM_HIST_BINS, SG_MUTUAL, SG_INMAX, SG_ISOL, SG_COMPS, SG_LARGEST, SG_N };
-// full strategy
-enum { SF_NUP = 0, SF_MIN, SF_MAX, SF_SUM, SF_AGREE, SF_N };
-constexpr uint32_t SH_NPB = BLK;      // nodes a k_sh_rows / k_sh_inv block takes: 64 a wave
-
-// a row of n <= PSIM_SVIEW_CAP ids, entry l in lane l of `a`, entry 64 + l in
-// lane l of `b` (lanes past n: PSIM_NONE, never loaded)
-DEV void sh_row_load(const uint32_t* __restrict__ row, uint32_t n, uint32_t& a, uint32_t& b) {
-    const uint32_t l = lane_id();
-    a = l < n ? row[l] : PSIM_NONE;
-    b = n > 64 && 64 + l < n ? row[64 + l] : PSIM_NONE;
-}
-// fa / fb: the lane's entry is the first occurrence of its id in the row
-DEV void sh_row_first(uint32_t a, uint32_t b, uint32_t n, bool& fa, bool& fb) {
-    const uint32_t l = lane_id();
-    fa = l < n; fb = 64 + l < n;
-    for (uint32_t j = 0; j + 1 < n; j++) {            // (uniform: n is)
-        const uint32_t v = j < 64 ? shfl(a, (int)j) : shfl(b, (int)(j - 64));
-        if (l > j && a == v) fa = false;
-        if (64 + l > j && b == v) fb = false;
-    }
-}
-DEV uint32_t sh_wave_sum(uint32_t v) {
-    for (int d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
-DEV bool sh_live(const uint8_t* __restrict__ flags, uint32_t N, uint32_t id) {
-    return id < N && (flags[id] & F_UP);
-}
-
-// off == nullptr: the count pass (statistics into sl, the node's link count
-// into cnt[lo + i]); else the pack pass (the links into adj at off[lo + i])
-__global__ void __launch_bounds__(BLK) k_sh_rows(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ sview,
-                                                 const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n,
-                                                 uint32_t N, uint32_t v2, uint8_t* cnt,
-                                                 const uint32_t* __restrict__ off, uint32_t* adj,
-                                                 unsigned long long* sl) {
-    __shared__ unsigned long long sh[SL_N];
-    for (uint32_t j = threadIdx.x; j < SL_N; j += blockDim.x) sh[j] = 0;
-    __syncthreads();
-    const uint32_t l = lane_id();
-    const uint32_t base = blockIdx.x * SH_NPB + (threadIdx.x >> 6) * 64;     // this wave's first node
-    const uint32_t mine = base + l;
-    uint32_t vn = 0, in_n = 0, o = 0, my_cnt = 0;
-    if (mine < n && (flags[lo + mine] & F_UP)) {
-        vn = min((uint32_t)hdr[mine].act_n, (uint32_t)PSIM_SVIEW_CAP);
-        in_n = hdr[mine].pas_n;
-        if (off) o = off[lo + mine];
-    }
-    const uint64_t up = ballot(mine < n && (flags[lo + mine] & F_UP));
-    uint64_t todo = off ? ballot(vn != 0) : up;
-    unsigned long long s_vsum = 0, s_isum = 0, s_dang = 0, s_self = 0, s_dup = 0, s_vmax = 0;
-    while (todo) {                                    // (uniform)
-        const int k = ffs64(todo);
-        todo &= todo - 1;
-        const uint32_t i = base + (uint32_t)k, me = lo + i;
-        const uint32_t len = shfl(vn, k);
-        uint32_t a, b;
-        bool fa, fb;
-        sh_row_load(sview + (size_t)i * PSIM_SVIEW_CAP, len, a, b);
-        sh_row_first(a, b, len, fa, fb);
-        const uint64_t oa = ballot(fa && a != me), ob = ballot(fb && b != me);
-        const uint64_t la = ballot(fa && a != me && sh_live(flags, N, a));
-        const uint64_t lb = ballot(fb && b != me && sh_live(flags, N, b));
-        if (off) {
-            const uint32_t at = shfl(o, k);
-            if ((la >> l) & 1) adj[at + popc(la & lt_mask())] = a;
-            if ((lb >> l) & 1) adj[at + popc(la) + popc(lb & lt_mask())] = b;
-            continue;
-        }
-        const uint32_t links = popc(la) + popc(lb), others = popc(oa) + popc(ob);
-        const uint32_t distinct = popc(ballot(fa)) + popc(ballot(fb));
-        if (l == (uint32_t)k) my_cnt = links;
-        s_vsum += len; s_dang += others - links; s_self += distinct - others; s_dup += len - distinct;
-        s_vmax = len > s_vmax ? len : s_vmax;
-        const uint32_t inn = v2 ? shfl(in_n, k) : 0;
-        s_isum += inn;
-        if (l == 0) {
-            atomicAdd(&sh[SL_VFILL * PSIM_HIST_BINS + hbin(len)], 1ull);
-            atomicAdd(&sh[SL_OUT * PSIM_HIST_BINS + hbin(others)], 1ull);
-            if (v2) atomicAdd(&sh[SL_IFILL * PSIM_HIST_BINS + hbin(inn)], 1ull);
-        }
-    }
-    if (off) return;
-    if (mine < n) cnt[lo + mine] = (uint8_t)my_cnt;
-    if (l == 0) {
-        atomicAdd(&sh[SL_NUP], (unsigned long long)popc(up));
-        atomicAdd(&sh[SL_VSUM], s_vsum); atomicAdd(&sh[SL_ISUM], s_isum); atomicAdd(&sh[SL_DANG], s_dang);
-        atomicAdd(&sh[SL_SELF], s_self); atomicAdd(&sh[SL_DUP], s_dup); atomicMax(&sh[SL_VMAX], s_vmax);
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < SL_N; j += blockDim.x) {
-        if (!sh[j]) continue;
-        if (j == SL_VMAX) atomicMax(&sl[j], sh[j]);
-        else atomicAdd(&sl[j], sh[j]);
-    }
-}
-
-// is `id` in node p's CSR row?
-DEV bool sh_has(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt, const uint32_t* __restrict__ adj,
-                uint32_t p, uint32_t id) {
-    const uint32_t* row = adj + off[p];
-    for (uint32_t q = 0, c = cnt[p]; q < c; q++)
-        if (row[q] == id) return true;
-    return false;
-}
-
-// scamp v2: the in_view rows of the local nodes against the CSR -- the
-// distinct live (i, j != i) with j in i's in_view, and those with j -> i a link
-__global__ void __launch_bounds__(BLK) k_sh_inv(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ sinv,
-                                                const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n,
-                                                uint32_t N, const uint32_t* __restrict__ off,
-                                                const uint8_t* __restrict__ cnt, const uint32_t* __restrict__ adj,
-                                                unsigned long long* sl) {
-    const uint32_t l = lane_id();
-    const uint32_t base = blockIdx.x * SH_NPB + (threadIdx.x >> 6) * 64;
-    const uint32_t mine = base + l;
-    uint32_t in_n = 0;
-    if (mine < n && (flags[lo + mine] & F_UP)) in_n = min((uint32_t)hdr[mine].pas_n, (uint32_t)PSIM_SVIEW_CAP);
-    uint64_t todo = ballot(in_n != 0);
-    uint32_t ivl = 0, ivc = 0;                        // (per lane)
-    while (todo) {                                    // (uniform)
-        const int k = ffs64(todo);
-        todo &= todo - 1;
-        const uint32_t i = base + (uint32_t)k, me = lo + i;
-        const uint32_t len = shfl(in_n, k);
-        uint32_t a, b;
-        bool fa, fb;
-        sh_row_load(sinv + (size_t)i * PSIM_SVIEW_CAP, len, a, b);
-        sh_row_first(a, b, len, fa, fb);
-        if (fa && a != me && sh_live(flags, N, a)) { ivl++; ivc += sh_has(off, cnt, adj, a, me) ? 1u : 0u; }
-        if (fb && b != me && sh_live(flags, N, b)) { ivl++; ivc += sh_has(off, cnt, adj, b, me) ? 1u : 0u; }
-    }
-    ivl = sh_wave_sum(ivl); ivc = sh_wave_sum(ivc);
-    if (l == 0 && ivl) atomicAdd(&sl[SL_IVL], (unsigned long long)ivl);
-    if (l == 0 && ivc) atomicAdd(&sl[SL_IVC], (unsigned long long)ivc);
-}
-
-// per rank r (one thread): its first row offset base[r] = E[r * per] and, in
-// tot[0], the largest number of links a rank holds (E: the exclusive scan of
-// the counts, npad + 1 entries)
-__global__ void k_sh_rank_tot(const uint32_t* __restrict__ E, uint32_t per, uint32_t W, uint32_t npad,
-                              uint32_t* base, unsigned long long* tot) {
-    if (blockIdx.x || threadIdx.x) return;
-    unsigned long long mx = 0;
-    for (uint32_t r = 0; r < W; r++) {
-        const uint32_t b = E[min(npad, r * per)], e = E[min(npad, (r + 1) * per)];
-        base[r] = b;
-        mx = max(mx, (unsigned long long)(e - b));
-    }
-    tot[0] = mx;
-}
-// rank r's rows start at r * slot: E[i] -> the row's place in the gathered CSR
-__global__ void k_sh_shift(uint32_t* E, uint32_t npad, uint32_t per, uint32_t slot,
-                           const uint32_t* __restrict__ base) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npad) return;
-    const uint32_t r = i / per;
-    E[i] = E[i] - base[r] + r * slot;
-}
-
-// the CSR's links: in-degrees, the link count, the links whose reverse exists
-__global__ void k_sh_links(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
-                           const uint32_t* __restrict__ adj, uint32_t n, uint32_t* indeg, unsigned long long* sg) {
-    __shared__ unsigned long long sh[2];
-    if (threadIdx.x < 2) sh[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t c = i < n ? cnt[i] : 0;
-    if (c) {
-        const uint32_t* row = adj + off[i];
-        uint32_t m = 0;
-        for (uint32_t k = 0; k < c; k++) {
-            const uint32_t p = row[k];
-            if (p >= n) continue;                     // (never: the pack pass keeps live ids < N)
-            atomicAdd(&indeg[p], 1u);
-            m += sh_has(off, cnt, adj, p, i) ? 1u : 0u;
-        }
-        atomicAdd(&sh[0], (unsigned long long)c);
-        if (m) atomicAdd(&sh[1], (unsigned long long)m);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && sh[threadIdx.x]) atomicAdd(&sg[SG_LINKS + threadIdx.x], sh[threadIdx.x]);
-}
-
-__global__ void k_sh_in(const uint32_t* __restrict__ indeg, const uint8_t* __restrict__ cnt,
-                        const uint8_t* __restrict__ flags, uint32_t n, unsigned long long* sg) {
-    __shared__ unsigned long long sh[SG_ISOL + 1];
-    for (uint32_t j = threadIdx.x; j <= SG_ISOL; j += blockDim.x) sh[j] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (flags[i] & F_UP)) {
-        const uint32_t d = indeg[i];
-        atomicAdd(&sh[hbin(d)], 1ull);
-        atomicMax(&sh[SG_INMAX], (unsigned long long)d);
-        if (!d && !cnt[i]) atomicAdd(&sh[SG_ISOL], 1ull);
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j <= SG_ISOL; j += blockDim.x) {
-        if (!sh[j]) continue;                         // (the link words stay zero here: k_sh_links')
-        if (j == SG_INMAX) atomicMax(&sg[j], sh[j]);
-        else atomicAdd(&sg[j], sh[j]);
-    }
-}
-
-// full strategy: the lowest live id (low: preset to PSIM_NONE; the flags are
-// replicated, so any shard finds it), then a wave per node over its member
-// row -- |add & ~remove| and its equality with the lowest live node's (ref:
-// that row, wherever it lives); the remove halves are read only once a
-// removal exists
-__global__ void k_sh_low(const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n, uint32_t* low) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (flags[lo + i] & F_UP)) atomicMin(low, i);
-}
-__global__ void __launch_bounds__(BLK) k_sh_full(const uint32_t* __restrict__ fbits, const uint8_t* __restrict__ flags,
-                                                 uint32_t lo, uint32_t n, uint32_t fw, uint32_t tomb,
-                                                 const uint32_t* __restrict__ ref, unsigned long long* sf) {
-    const uint32_t i = blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);         // (uniform per wave)
-    if (i >= n || !(flags[lo + i] & F_UP)) return;
-    const uint32_t* row = fbits + (size_t)i * 2 * fw;
-    uint32_t c = 0;
-    bool differs = false;
-    for (uint32_t w = lane_id(); w < fw; w += 64) {
-        const uint32_t q = tomb ? row[w] & ~row[fw + w] : row[w];
-        const uint32_t r = tomb ? ref[w] & ~ref[fw + w] : ref[w];
-        c += (uint32_t)__popc(q);
-        differs |= q != r;
-    }
-    c = sh_wave_sum(c);
-    const bool agree = ballot(differs) == 0;
-    if (lane_id() == 0) {
-        atomicAdd(&sf[SF_NUP], 1ull);
-        atomicMin(&sf[SF_MIN], (unsigned long long)c);
-        atomicMax(&sf[SF_MAX], (unsigned long long)c);
-        atomicAdd(&sf[SF_SUM], (unsigned long long)c);
-        if (agree) atomicAdd(&sf[SF_AGREE], 1ull);
-    }
-}
-
-// ------------------------------------- path lengths and clustering --
-// psim_get_graph_metrics.  Every kernel reads the link set L as rows: node
-// i's cnt[i] ids at adj + off[i] (the pluggable handles' CSR, as k_sh_rows
-// packs it: distinct, != i, live) or, off == nullptr, at
-// adj + i * PSIM_ACTIVE_CAP (HyParView's rows after k_gm_filter, the same
-// three properties).
-//   k_gm_cluster_hv / k_gm_cluster   closed_i = sum over a in N(i) of
-//                      |N(a) & N(i)| (no row holds its own node, so b != a)
-//   k_gm_init / k_gm_push / k_gm_level   the bit-parallel BFS: bit j of a
-//                      node's word = reached from source slot j
-enum { GM_NUP = 0, GM_LINKS, GM_NODES, GM_CLOSED, GM_PAIRS, GM_Q32, GM_N };
-constexpr uint32_t GM_TAB = 256;      // k_gm_cluster: hash slots a wave keeps for one N(i) (<= PSIM_SVIEW_CAP ids)
-
-__global__ void k_gm_filter(const uint8_t* __restrict__ gan, const uint32_t* __restrict__ gact,
-                            const uint8_t* __restrict__ flags, uint32_t n, uint32_t* fadj, uint8_t* fcnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t c = 0;
-    if (flags[i] & F_UP) {
-        const uint32_t* row = gact + (size_t)i * PSIM_ACTIVE_CAP;
-        const uint32_t len = min((uint32_t)gan[i], (uint32_t)PSIM_ACTIVE_CAP);
-        for (uint32_t k = 0; k < len; k++) {
-            const uint32_t p = row[k];
-            if (p == i || p >= n || !(flags[p] & F_UP)) continue;
-            bool dup = false;
-            for (uint32_t q = 0; q < k; q++) dup |= row[q] == p;
-            if (!dup) fadj[(size_t)i * PSIM_ACTIVE_CAP + c++] = p;
-        }
-    }
-    fcnt[i] = (uint8_t)c;
-}
-
-// a node's share of the clustering sums, into the block's LDS words
-DEV void gm_cluster_add(unsigned long long* sh, uint32_t k, uint32_t closed) {
-    atomicAdd(&sh[GM_NUP], 1ull);
-    if (k) atomicAdd(&sh[GM_LINKS], (unsigned long long)k);
-    if (k < 2) return;
-    const unsigned long long pairs = (unsigned long long)k * (k - 1);
-    atomicAdd(&sh[GM_NODES], 1ull);
-    atomicAdd(&sh[GM_PAIRS], pairs);
-    if (closed) {
-        atomicAdd(&sh[GM_CLOSED], (unsigned long long)closed);
-        atomicAdd(&sh[GM_Q32], ((unsigned long long)closed << 32) / pairs);
-    }
-}
-
-// HyParView rows: 8 lanes a node, lane g takes neighbour g's row
-__global__ void __launch_bounds__(BLK) k_gm_cluster_hv(const uint8_t* __restrict__ cnt,
-                                                       const uint32_t* __restrict__ adj,
-                                                       const uint8_t* __restrict__ flags, uint32_t n,
-                                                       unsigned long long* gm) {
-    static_assert(PSIM_ACTIVE_CAP == 8, "one 8-lane group per node");
-    __shared__ unsigned long long sh[GM_N];
-    if (threadIdx.x < GM_N) sh[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) / PSIM_ACTIVE_CAP, g = threadIdx.x % PSIM_ACTIVE_CAP;
-    const bool up = i < n && (flags[i] & F_UP);
-    const uint32_t k = up ? cnt[i] : 0;
-    uint32_t mine[PSIM_ACTIVE_CAP];
-#pragma unroll
-    for (uint32_t r = 0; r < PSIM_ACTIVE_CAP; r++) mine[r] = r < k ? adj[(size_t)i * PSIM_ACTIVE_CAP + r] : PSIM_NONE;
-    uint32_t c = 0;
-    if (g < k && k >= 2) {
-        const uint32_t a = adj[(size_t)i * PSIM_ACTIVE_CAP + g];
-        const uint32_t* row = adj + (size_t)a * PSIM_ACTIVE_CAP;
-        for (uint32_t q = 0, ka = cnt[a]; q < ka; q++) {
-            const uint32_t b = row[q];
-#pragma unroll
-            for (uint32_t r = 0; r < PSIM_ACTIVE_CAP; r++) c += mine[r] == b ? 1u : 0u;
-        }
-    }
-    for (int d = PSIM_ACTIVE_CAP / 2; d; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
-    if (up && g == 0) gm_cluster_add(sh, k, c);
-    __syncthreads();
-    if (threadIdx.x < GM_N && sh[threadIdx.x]) atomicAdd(&gm[threadIdx.x], sh[threadIdx.x]);
-}
-
-DEV uint32_t gm_hash(uint32_t id) { return (id * 2654435761u) >> 24; }     // (GM_TAB = 2^8 slots)
-
-// CSR rows (up to PSIM_SVIEW_CAP ids): a wave a node.  N(i) sits in the
-// wave's LDS hash table (at most half full); each neighbour's row is read
-// coalesced, two ids a lane as sh_row_load holds a view, and probed against it
-__global__ void __launch_bounds__(BLK) k_gm_cluster(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
-                                                    const uint32_t* __restrict__ adj,
-                                                    const uint8_t* __restrict__ flags, uint32_t n,
-                                                    unsigned long long* gm) {
-    static_assert(GM_TAB == 256 && GM_TAB >= 2 * PSIM_SVIEW_CAP, "gm_hash gives 8 bits; the table stays half empty");
-    __shared__ uint32_t tab_all[BLK / 64][GM_TAB];
-    __shared__ unsigned long long sh[GM_N];
-    const uint32_t w = threadIdx.x >> 6, l = lane_id();
-    uint32_t* tab = tab_all[w];
-    for (uint32_t q = l; q < GM_TAB; q += 64) tab[q] = PSIM_NONE;
-    if (threadIdx.x < GM_N) sh[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * (BLK / 64) + w;                          // (uniform per wave)
-    const bool up = i < n && (flags[i] & F_UP);
-    const uint32_t k = up ? min((uint32_t)cnt[i], (uint32_t)PSIM_SVIEW_CAP) : 0;
-    uint32_t a = PSIM_NONE, b = PSIM_NONE;
-    if (k >= 2) {
-        sh_row_load(adj + off[i], k, a, b);
-        for (int half = 0; half < 2; half++) {
-            const uint32_t id = half ? b : a;
-            if (id == PSIM_NONE) continue;
-            uint32_t s = gm_hash(id);
-            for (uint32_t t = 0; t < GM_TAB; t++, s = (s + 1) % GM_TAB)      // (ends at a free slot: <= 128 ids)
-                if (atomicCAS(&tab[s], PSIM_NONE, id) == PSIM_NONE) break;
-        }
-    }
-    __syncthreads();
-    uint32_t c = 0;
-    if (k >= 2) {
-        for (uint32_t t = 0; t < k; t++) {                                   // (uniform)
-            const uint32_t p = t < 64 ? shfl(a, (int)t) : shfl(b, (int)(t - 64));
-            uint32_t x, y;
-            sh_row_load(adj + off[p], min((uint32_t)cnt[p], (uint32_t)PSIM_SVIEW_CAP), x, y);
-            for (int half = 0; half < 2; half++) {
-                const uint32_t id = half ? y : x;
-                if (id == PSIM_NONE) continue;
-                uint32_t s = gm_hash(id);
-                for (uint32_t u = 0; u < GM_TAB; u++, s = (s + 1) % GM_TAB) {
-                    const uint32_t v = tab[s];
-                    if (v == id) c++;
-                    if (v == id || v == PSIM_NONE) break;
-                }
-            }
-        }
-        c = sh_wave_sum(c);
-    }
-    if (up && l == 0) gm_cluster_add(sh, k, c);
-    __syncthreads();
-    if (threadIdx.x < GM_N && sh[threadIdx.x]) atomicAdd(&gm[threadIdx.x], sh[threadIdx.x]);
-}
-
-// source slot j starts at sources[j] if that node is live; live: the mask of
-// such slots (one block of 64 threads; the sources are distinct and < n)
-__global__ void k_gm_init(const uint32_t* __restrict__ sources, uint32_t ns, const uint8_t* __restrict__ flags,
-                          unsigned long long* seen, unsigned long long* front, unsigned long long* live) {
-    const uint32_t j = threadIdx.x;
-    const bool on = j < ns && (flags[sources[j]] & F_UP);
-    if (on) { seen[sources[j]] = 1ull << j; front[sources[j]] = 1ull << j; }
-    const uint64_t m = ballot(on);
-    if (j == 0) *live = m;
-}
-
-// a node on the frontier ORs its word into each out-neighbour that lacks a bit of it
-__global__ void k_gm_push(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
-                          const uint32_t* __restrict__ adj, uint32_t n,
-                          const unsigned long long* __restrict__ front,
-                          const unsigned long long* __restrict__ seen, unsigned long long* next) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long f = front[i];
-    if (!f) return;
-    const uint32_t* row = adj + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP);
-    for (uint32_t k = 0, c = cnt[i]; k < c; k++) {
-        const uint32_t p = row[k];
-        if (f & ~seen[p]) atomicOr(&next[p], f);
-    }
-}
-
-// the level's new bits: into seen, the next frontier, lv[0] (their OR over
-// all nodes), lv[1] (their number) and reach[j] per slot; reduced in the wave,
-// then in the block's LDS, and only where a wave saw a new bit
-__global__ void __launch_bounds__(BLK) k_gm_level(uint32_t n, unsigned long long* next, unsigned long long* seen,
-                                                  unsigned long long* front, unsigned long long* lv,
-                                                  unsigned long long* reach) {
-    __shared__ unsigned long long sh_reach[PSIM_GRAPH_SOURCES], sh_lv[2];
-    if (threadIdx.x < PSIM_GRAPH_SOURCES) sh_reach[threadIdx.x] = 0;
-    if (threadIdx.x < 2) sh_lv[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long nw = 0;
-    if (i < n) {
-        const unsigned long long nx = next[i];
-        if (nx) {
-            const unsigned long long s = seen[i];
-            nw = nx & ~s;
-            next[i] = 0;
-            if (nw) seen[i] = s | nw;
-        }
-        if (front[i] != nw) front[i] = nw;
-    }
-    if (ballot(nw != 0)) {                            // (uniform)
-        uint32_t lo = (uint32_t)nw, hi = (uint32_t)(nw >> 32);
-        for (int d = 32; d; d >>= 1) { lo |= (uint32_t)__shfl_xor((int)lo, d); hi |= (uint32_t)__shfl_xor((int)hi, d); }
-        const uint32_t cnt = sh_wave_sum(popc(nw));
-        uint64_t todo = ((uint64_t)hi << 32) | lo;
-        if (lane_id() == 0) { atomicOr(&sh_lv[0], (unsigned long long)todo); atomicAdd(&sh_lv[1], (unsigned long long)cnt); }
-        while (todo) {
-            const int j = ffs64(todo);
-            todo &= todo - 1;
-            const uint32_t c = popc(ballot((nw >> j) & 1));
-            if (lane_id() == 0) atomicAdd(&sh_reach[j], (unsigned long long)c);
-        }
-    }
-    __syncthreads();
-    if (!sh_lv[0]) return;                            // (uniform per block)
-    if (threadIdx.x < PSIM_GRAPH_SOURCES && sh_reach[threadIdx.x]) atomicAdd(&reach[threadIdx.x], sh_reach[threadIdx.x]);
-    if (threadIdx.x == 0) { atomicOr(&lv[0], sh_lv[0]); atomicAdd(&lv[1], sh_lv[1]); }
-}
-
-// ------------------------------------------- reach under mass failure --
-// psim_get_resilience (psim_resilience in the header defines every field):
-// the word of the k_gm_* BFS spent on 64 failure cases, bit j of alive[v] =
-// "v is in A_j".  The rows are those k_gm_push reads.
-//   k_rs_live     the mask of cases whose source is up
-//   k_rs_alive    alive[v], and the BFS seeded from it: seen[v] = ~alive[v]
-//                 plus the bits of the cases that start at v, front[v] = those
-//                 bits; a failed or down bit is never new to k_gm_level
-//   k_rs_census   over every link (i, p): m = alive[i] & alive[p] counted per
-//                 bit into links_alive, ORed into inw[p]; no_out from the
-//                 bits of alive[i] that no link kept
-//   k_rs_sweep    alive[] and no_in per bit
-// The case table `par`: RS_SRC, RS_THR and RS_SALT by the host's order (cases
-// of one salt side by side, so a node pays one inner mix64 per distinct salt),
-// RS_SLOT the slot of each.
-enum { RS_SRC = 0, RS_THR = 64, RS_SALT = 128, RS_SLOT = 192, RS_PAR = 256 };
-enum { RS_ALIVE = 0, RS_LINKS = 64, RS_NOOUT = 128, RS_NOIN = 192, RS_NUP = 256, RS_L = 257, RS_LIVE = 258, RS_N = 259 };
-
-DEV uint64_t rs_wave_or(uint64_t w) {
-    uint32_t lo = (uint32_t)w, hi = (uint32_t)(w >> 32);
-    for (int d = 32; d; d >>= 1) { lo |= (uint32_t)__shfl_xor((int)lo, d); hi |= (uint32_t)__shfl_xor((int)hi, d); }
-    return ((uint64_t)hi << 32) | lo;
-}
-// the wave's lanes holding bit j of w, for every j set in some lane, into the
-// block's 64-word tile: one ballot per such bit, as k_gm_level counts `reach`
-DEV void rs_tile_add(unsigned long long* tile, uint64_t w) {
-    uint64_t todo = rs_wave_or(w);                    // (uniform)
-    while (todo) {
-        const int j = ffs64(todo);
-        todo &= todo - 1;
-        const uint32_t c = popc(ballot((w >> j) & 1));
-        if (lane_id() == 0) atomicAdd(&tile[j], (unsigned long long)c);
-    }
-}
-
-__global__ void k_rs_live(const uint32_t* __restrict__ par, uint32_t nc, const uint8_t* __restrict__ flags,
-                          unsigned long long* rs) {
-    const uint32_t q = threadIdx.x;                   // (one block of 64 threads; the sources are < n)
-    const bool on = q < nc && (flags[par[RS_SRC + q]] & F_UP);
-    if (on) atomicOr(&rs[RS_LIVE], 1ull << par[RS_SLOT + q]);
-}
-
-__global__ void __launch_bounds__(BLK) k_rs_alive(const uint32_t* __restrict__ par, uint32_t nc, uint64_t fail_seed,
-                                                  const uint8_t* __restrict__ flags, uint32_t n,
-                                                  unsigned long long* rs, unsigned long long* alive,
-                                                  unsigned long long* seen, unsigned long long* front) {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool up = v < n && (flags[v] & F_UP);
-    const unsigned long long live = rs[RS_LIVE];      // (k_rs_live ran before on the stream)
-    unsigned long long a = 0, sb = 0;
-    if (up) {
-        uint64_t inner = 0;
-        for (uint32_t q = 0; q < nc; q++) {           // (uniform)
-            const uint32_t salt = par[RS_SALT + q];
-            if (!q || salt != par[RS_SALT + q - 1]) inner = mix64(((uint64_t)salt << 32) | v);
-            const uint32_t u = (uint32_t)(mix64(fail_seed ^ inner) >> 32);
-            const unsigned long long bit = 1ull << par[RS_SLOT + q];
-            const bool src = par[RS_SRC + q] == v;
-            if (src || u >= par[RS_THR + q]) a |= bit;
-            if (src) sb |= bit;
-        }
-        a &= live; sb &= live;
-    }
-    if (v < n) { alive[v] = a; seen[v] = ~a | sb; front[v] = sb; }
-    const uint32_t c = popc(ballot(up));
-    if (c && lane_id() == 0) atomicAdd(&rs[RS_NUP], (unsigned long long)c);
-}
-
-__global__ void __launch_bounds__(BLK) k_rs_census(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
-                                                   const uint32_t* __restrict__ adj,
-                                                   const uint8_t* __restrict__ flags, uint32_t n,
-                                                   const unsigned long long* __restrict__ alive,
-                                                   unsigned long long* inw, unsigned long long* rs) {
-    static_assert(PSIM_SVIEW_CAP < 256 && PSIM_ACTIVE_CAP < 256, "a row's links per case fit the 8 counter planes");
-    __shared__ unsigned long long sh_links[PSIM_FAIL_CASES], sh_noout[PSIM_FAIL_CASES], sh_l;
-    if (threadIdx.x < PSIM_FAIL_CASES) { sh_links[threadIdx.x] = 0; sh_noout[threadIdx.x] = 0; }
-    if (threadIdx.x == 0) sh_l = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool up = i < n && (flags[i] & F_UP);
-    const uint32_t c = up ? cnt[i] : 0;
-    const unsigned long long a = up ? alive[i] : 0;
-    // plane b holds bit b of this node's link count of every case
-    unsigned long long pl[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ho = 0;
-    if (a) {
-        const uint32_t* row = adj + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP);
-        for (uint32_t k = 0; k < c; k++) {
-            const uint32_t p = row[k];
-            const unsigned long long m = a & alive[p];
-            if (!m) continue;
-            ho |= m;
-            if (m & ~inw[p]) atomicOr(&inw[p], m);
-            unsigned long long carry = m;
-#pragma unroll
-            for (int b = 0; b < 8; b++) { const unsigned long long t = pl[b] & carry; pl[b] ^= carry; carry = t; }
-        }
-    }
-    const uint32_t lsum = sh_wave_sum(c);
-    if (lsum && lane_id() == 0) atomicAdd(&sh_l, (unsigned long long)lsum);
-    if (ballot(a != 0)) {                             // (uniform)
-        rs_tile_add(sh_noout, a & ~ho);
-        uint64_t todo = rs_wave_or(ho);
-        while (todo) {
-            const int j = ffs64(todo);
-            todo &= todo - 1;
-            uint32_t s = 0;
-#pragma unroll
-            for (int b = 0; b < 8; b++) s += popc(ballot((pl[b] >> j) & 1)) << b;
-            if (lane_id() == 0) atomicAdd(&sh_links[j], (unsigned long long)s);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < PSIM_FAIL_CASES) {
-        if (sh_links[threadIdx.x]) atomicAdd(&rs[RS_LINKS + threadIdx.x], sh_links[threadIdx.x]);
-        if (sh_noout[threadIdx.x]) atomicAdd(&rs[RS_NOOUT + threadIdx.x], sh_noout[threadIdx.x]);
-    }
-    if (threadIdx.x == 0 && sh_l) atomicAdd(&rs[RS_L], sh_l);
-}
-
-__global__ void __launch_bounds__(BLK) k_rs_sweep(uint32_t n, const unsigned long long* __restrict__ alive,
-                                                  const unsigned long long* __restrict__ inw,
-                                                  unsigned long long* rs) {
-    __shared__ unsigned long long sh_alive[PSIM_FAIL_CASES], sh_noin[PSIM_FAIL_CASES];
-    if (threadIdx.x < PSIM_FAIL_CASES) { sh_alive[threadIdx.x] = 0; sh_noin[threadIdx.x] = 0; }
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long a = i < n ? alive[i] : 0;
-    if (ballot(a != 0)) {                             // (uniform)
-        rs_tile_add(sh_alive, a);
-        rs_tile_add(sh_noin, a & ~inw[i < n ? i : 0]);
-    }
-    __syncthreads();
-    if (threadIdx.x < PSIM_FAIL_CASES) {
-        if (sh_alive[threadIdx.x]) atomicAdd(&rs[RS_ALIVE + threadIdx.x], sh_alive[threadIdx.x]);
-        if (sh_noin[threadIdx.x]) atomicAdd(&rs[RS_NOIN + threadIdx.x], sh_noin[threadIdx.x]);
-    }
-}
-
-// ------------------------------------------------------ broadcast tree --
-// psim_get_tree_metrics: root R's eager / lazy sets of every live node
-// (psim_tree_metrics in the header defines every field).
-//   k_tm_rows (count)  LN lanes a node; finds R's slot in the root row, holds
-//                      the eager and the lazy run RT_SET / LN entries a lane,
-//                      decodes, drops self, tests liveness, marks the first
-//                      occurrence of a peer over both identity forms by a
-//                      compare against every lane of the group, tests the
-//                      active view, counts the entry-level fields and writes
-//                      |E_i| (a byte, by global id)
-//   scan_excl          the counts (all-gathered across ranks) -> row offsets
-//   k_tm_rows (pack)   the same group writes E_i at its offset and adds the
-//                      in-degrees
-//   k_tm_sym           (i, p) in T: is i in p's row?
-//   k_tm_bfs           one level of a single-source BFS over CSR or
-//                      HyParView rows, depths in an N-word array
-//   k_tm_final         the in-degree histogram and the two depth arrays
-// tm layout (summed over ranks): two histograms, then scalars
-enum { TM_EOUT = 0, TM_LOUT = 1, TM_NUP = 2 * PSIM_HIST_BINS, TM_SLOT, TM_EENT, TM_LENT, TM_ELINKS, TM_LLINKS,
-       TM_BOTH, TM_FORMS, TM_SELF, TM_EDEAD, TM_LDEAD, TM_ENM, TM_LNM, TM_N };
-constexpr uint32_t TM_SCALARS = TM_N - TM_NUP;
-// tf layout (over the whole CSR, the same on every rank): the in-degree histogram, then scalars
-enum { TF_LFR = PSIM_HIST_BINS, TF_OREACH, TF_BOTH, TF_DSUM, TF_LSUM, TF_DEEPER, TF_SHALLOWER, TF_N };
-
-// a run of at most RT_SET entries held by a group of LN lanes: entry
-// c * LN + g in e[c] of the group's lane g
-template <uint32_t LN>
-struct TmRun {
-    static constexpr uint32_t C = RT_SET / LN;
-    uint32_t e[C], p[C];
-    bool keep[C];                         // the entry names a live node other than the owner
-    uint32_t n;
-};
-
-// loads the run; counts the lane's entries that name the owner / a dead node
-template <uint32_t LN>
-DEV void tm_load(TmRun<LN>& r, const uint32_t* __restrict__ src, uint32_t n, uint32_t me,
-                 const uint8_t* __restrict__ flags, uint32_t N, uint32_t& self, uint32_t& dead) {
-    const uint32_t g = lane_id() % LN;
-    r.n = n;
-#pragma unroll
-    for (uint32_t c = 0; c < TmRun<LN>::C; c++) {
-        const bool v = c * LN + g < n;
-        r.e[c] = v ? src[c * LN + g] : PSIM_NONE;
-        r.p[c] = r.e[c] & ~PSIM_MAP_BIT;
-        const bool own = v && r.p[c] == me, live = v && sh_live(flags, N, r.p[c]);
-        r.keep[c] = live && !own;
-        self += own ? 1u : 0u;
-        dead += v && !own && !live ? 1u : 0u;
-    }
-}
-
-// every entry of run b, in order, against the lane's entries of run a:
-// dup[c]: an entry of b before position c * LN + g names the same node (a == b:
-// the entry is no first occurrence); hit[c]: some entry of b names it;
-// atom[c] / map[c]: b holds the node's plain / PSIM_MAP_BIT form.  The loop
-// bounds are the same in all lanes of a group, and a lane reads its own group only
-template <uint32_t LN>
-DEV void tm_match(const TmRun<LN>& a, const TmRun<LN>& b, bool* dup, bool* hit, bool* atom, bool* map) {
-    constexpr uint32_t C = TmRun<LN>::C;
-    const uint32_t l = lane_id(), g = l % LN, gb = l - g;
-#pragma unroll
-    for (uint32_t c = 0; c < C; c++) dup[c] = hit[c] = atom[c] = map[c] = false;
-#pragma unroll
-    for (uint32_t c2 = 0; c2 < C; c2++)
-        for (uint32_t y = 0; y < LN && c2 * LN + y < b.n; y++) {
-            const uint32_t ev = shfl(b.e[c2], (int)(gb + y)), pv = ev & ~PSIM_MAP_BIT;
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) {
-                const bool same = pv == a.p[c];
-                dup[c] |= same && c2 * LN + y < c * LN + g;
-                hit[c] |= same;
-                atom[c] |= ev == a.p[c];
-                map[c] |= ev == (a.p[c] | PSIM_MAP_BIT);
-            }
-        }
-}
-
-// off == nullptr: the count pass (statistics into tm, |E_i| into
-// cnt[lo + i]); else the pack pass (E_i into adj at off[lo + i], indeg)
-template <uint32_t LN>
-__global__ void __launch_bounds__(BLK) k_tm_rows(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ act,
-                                                 const uint32_t* __restrict__ pt_rt,
-                                                 const uint32_t* __restrict__ pt_eag,
-                                                 const uint32_t* __restrict__ pt_laz,
-                                                 const uint32_t* __restrict__ pt_com,
-                                                 const uint8_t* __restrict__ flags, uint32_t lo, uint32_t n,
-                                                 uint32_t N, uint32_t root, uint8_t* cnt,
-                                                 const uint32_t* __restrict__ off, uint32_t* adj, uint32_t* indeg,
-                                                 unsigned long long* tm) {
-    static_assert(LN == 16 || LN == 64, "a DPP row or a wave a node");
-    static_assert(PSIM_PT_ROOTS == 4 && RT_SET == 64, "the counts of a pool: one byte a slot, 64 entries");
-    constexpr uint32_t C = TmRun<LN>::C;
-    constexpr uint64_t GROUP = LN == 64 ? ~0ull : (1ull << (LN % 64)) - 1ull;     // a group's lanes of a ballot
-    __shared__ unsigned long long sh[TM_N];
-    for (uint32_t j = threadIdx.x; j < TM_N; j += blockDim.x) sh[j] = 0;
-    __syncthreads();
-    const uint32_t l = lane_id(), g = l % LN, gb = l - g;
-    const uint32_t i = (blockIdx.x * BLK + threadIdx.x) / LN, me = lo + i;
-    const bool up = i < n && (flags[me] & F_UP);
-    uint32_t s[TM_SCALARS] = {0};                     // the lane's share of the scalars
-    if (up) {                                         // (the same in all lanes of a group)
-        // R's slot, or the common set
-        const uint32_t* rt = pt_rt + (size_t)i * RT_WORDS;
-        int k = -1;
-        for (int q = PSIM_PT_ROOTS - 1; q >= 0; q--) k = rt[q] == (root | PSIM_MAP_BIT) ? q : k;
-        uint32_t en, ln = 0, eo = 0, zo = 0;
-        if (k >= 0) {
-            const uint32_t ce = rt[RT_EN], cl = rt[RT_LN];
-            for (int q = 0; q < k; q++) { eo += (ce >> (8 * q)) & 0xFFu; zo += (cl >> (8 * q)) & 0xFFu; }
-            eo = min(eo, RT_SET); zo = min(zo, RT_SET);
-            en = min((ce >> (8 * k)) & 0xFFu, RT_SET - eo);
-            ln = min((cl >> (8 * k)) & 0xFFu, RT_SET - zo);
-        } else {
-            en = min((uint32_t)hdr[i].com_n, (uint32_t)PSIM_PT_MEMBERS_CAP);
-        }
-        const uint32_t* er = k >= 0 ? pt_eag + (size_t)i * RT_SET + eo : pt_com + (size_t)i * PSIM_PT_MEMBERS_CAP;
-        TmRun<LN> E;
-        bool dup[C], hit[C], atom[C], map[C];
-        tm_load(E, er, en, me, flags, N, s[TM_SELF - TM_NUP], s[TM_EDEAD - TM_NUP]);
-        tm_match(E, E, dup, hit, atom, map);
-        // E_i: the first occurrences among the kept entries, packed in entry order
-        uint32_t ne = 0;
-        bool first[C];
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) {
-            first[c] = E.keep[c] && !dup[c];
-            const uint64_t b = (ballot(first[c]) >> gb) & GROUP;
-            if (off && first[c]) {
-                adj[off[me] + ne + popc(b & ((1ull << g) - 1ull))] = E.p[c];
-                atomicAdd(&indeg[E.p[c]], 1u);
-            }
-            ne += popc(b);
-        }
-        if (!off) {
-            const uint32_t an = min((uint32_t)hdr[i].act_n, (uint32_t)PSIM_ACTIVE_CAP);
-            uint32_t av[PSIM_ACTIVE_CAP];
-#pragma unroll
-            for (uint32_t q = 0; q < PSIM_ACTIVE_CAP; q++) av[q] = q < an ? act[(size_t)i * PSIM_ACTIVE_CAP + q] : PSIM_NONE;
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) {
-                if (!first[c]) continue;
-                bool mem = false;
-#pragma unroll
-                for (uint32_t q = 0; q < PSIM_ACTIVE_CAP; q++) mem |= av[q] == E.p[c];
-                s[TM_ENM - TM_NUP] += mem ? 0u : 1u;
-                s[TM_FORMS - TM_NUP] += atom[c] && map[c] ? 1u : 0u;
-            }
-            uint32_t nz = 0;
-            if (ln) {                                 // (the same in all lanes of a group)
-                TmRun<LN> Z;
-                bool zdup[C], inE[C];
-                tm_load(Z, pt_laz + (size_t)i * RT_SET + zo, ln, me, flags, N, s[TM_SELF - TM_NUP],
-                        s[TM_LDEAD - TM_NUP]);
-                tm_match(Z, Z, zdup, hit, atom, map);
-                tm_match(Z, E, dup, inE, atom, map);
-#pragma unroll
-                for (uint32_t c = 0; c < C; c++) {
-                    if (!Z.keep[c] || zdup[c]) continue;
-                    bool mem = false;
-#pragma unroll
-                    for (uint32_t q = 0; q < PSIM_ACTIVE_CAP; q++) mem |= av[q] == Z.p[c];
-                    nz++;
-                    s[TM_LNM - TM_NUP] += mem ? 0u : 1u;
-                    s[TM_BOTH - TM_NUP] += inE[c] ? 1u : 0u;
-                }
-                s[TM_LLINKS - TM_NUP] += nz;
-                for (int d = LN / 2; d; d >>= 1) nz += (uint32_t)__shfl_xor((int)nz, d);
-            }
-            if (g == 0) {
-                cnt[me] = (uint8_t)ne;
-                s[TM_NUP - TM_NUP] = 1; s[TM_SLOT - TM_NUP] = k >= 0 ? 1u : 0u;
-                s[TM_EENT - TM_NUP] = en; s[TM_LENT - TM_NUP] = ln; s[TM_ELINKS - TM_NUP] = ne;
-                atomicAdd(&sh[TM_EOUT * PSIM_HIST_BINS + hbin(ne)], 1ull);
-                atomicAdd(&sh[TM_LOUT * PSIM_HIST_BINS + hbin(nz)], 1ull);
-            }
-        }
-    }
-    if (off) return;
-#pragma unroll
-    for (uint32_t j = 0; j < TM_SCALARS; j++) {
-        const uint32_t v = sh_wave_sum(s[j]);
-        if (l == 0 && v) atomicAdd(&sh[TM_NUP + j], (unsigned long long)v);
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < TM_N; j += blockDim.x)
-        if (sh[j]) atomicAdd(&tm[j], sh[j]);
-}
-
-// the links of T whose reverse is a link of T (every process over the whole CSR)
-__global__ void k_tm_sym(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
-                         const uint32_t* __restrict__ adj, uint32_t n, unsigned long long* sym) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t c = 0;
-    if (i < n) {
-        const uint32_t* row = adj + off[i];
-        for (uint32_t k = 0, ci = cnt[i]; k < ci; k++) c += sh_has(off, cnt, adj, row[k], i) ? 1u : 0u;
-    }
-    c = sh_wave_sum(c);
-    if (lane_id() == 0 && c) atomicAdd(sym, (unsigned long long)c);
-}
-
-// level d of a single-source BFS (rows as k_gm_push reads them): a node at
-// depth d - 1 claims each out-neighbour that has no depth yet; found: the
-// nodes claimed
-__global__ void k_tm_bfs(const uint32_t* __restrict__ off, const uint8_t* __restrict__ cnt,
-                         const uint32_t* __restrict__ adj, uint32_t n, uint32_t d, uint32_t* depth,
-                         unsigned long long* found) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t c = 0;
-    if (i < n && depth[i] == d - 1) {
-        const uint32_t* row = adj + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP);
-        for (uint32_t k = 0, ci = cnt[i]; k < ci; k++) {
-            const uint32_t p = row[k];
-            if (p < n && depth[p] == PSIM_NONE && atomicCAS(&depth[p], PSIM_NONE, d) == PSIM_NONE) c++;
-        }
-    }
-    c = sh_wave_sum(c);
-    if (lane_id() == 0 && c) atomicAdd(found, (unsigned long long)c);
-}
-
-// per live node: its in-degree in T; dt / dl (nullptr: R is not live): its
-// depth over T and its distance over L (PSIM_NONE: none)
-__global__ void __launch_bounds__(BLK) k_tm_final(const uint32_t* __restrict__ indeg,
-                                                  const uint8_t* __restrict__ cnt,
-                                                  const uint8_t* __restrict__ flags, uint32_t n, uint32_t root,
-                                                  const uint32_t* __restrict__ dt,
-                                                  const uint32_t* __restrict__ dl, unsigned long long* tf) {
-    __shared__ unsigned long long sh[TF_N];
-    for (uint32_t j = threadIdx.x; j < TF_N; j += blockDim.x) sh[j] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t s[TF_N - TF_LFR] = {0};
-    if (i < n && (flags[i] & F_UP)) {
-        atomicAdd(&sh[hbin(indeg[i])], 1ull);
-        const uint32_t a = dt ? dt[i] : PSIM_NONE, b = dl ? dl[i] : PSIM_NONE;
-        if (a != PSIM_NONE) s[TF_LFR - TF_LFR] = cnt[i];
-        if (i != root) {
-            if (b != PSIM_NONE) s[TF_OREACH - TF_LFR] = 1;
-            if (a != PSIM_NONE && b != PSIM_NONE) {
-                s[TF_BOTH - TF_LFR] = 1; s[TF_DSUM - TF_LFR] = a; s[TF_LSUM - TF_LFR] = b;
-                s[TF_DEEPER - TF_LFR] = a > b ? 1u : 0u; s[TF_SHALLOWER - TF_LFR] = a < b ? 1u : 0u;
-            }
-        }
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < TF_N - TF_LFR; j++) {
-        const uint32_t v = sh_wave_sum(s[j]);         // (a wave's depths: 64 * 4096 at the most)
-        if (lane_id() == 0 && v) atomicAdd(&sh[TF_LFR + j], (unsigned long long)v);
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < TF_N; j += blockDim.x)
-        if (sh[j]) atomicAdd(&tf[j], sh[j]);
-}
-
 // ------------------------------------------------------- message trace --
 // psim_trace_watch ("Message trace"): after a round, the
 // records of the shard's next inbox that pass the watch, copied in inbox order
@@ -3055,7 +2042,7 @@ __global__ void __launch_bounds__(TR_BLK) k_trace_copy(const Msg* __restrict__ i
     __shared__ uint8_t sel[TR_WAVES][64];
     const uint32_t l = lane_id(), wv = threadIdx.x >> 6;
     // the matches of the blocks before this one (gridDim.x <= TR_BLK)
-    const uint32_t mine = sh_wave_sum(threadIdx.x < blockIdx.x ? cnt[threadIdx.x] : 0u);
+    const uint32_t mine = wave_sum(threadIdx.x < blockIdx.x ? cnt[threadIdx.x] : 0u);
     if (l == 0) wsum[wv] = mine;
     __syncthreads();
     unsigned long long rank0 = tot_in[0];
@@ -3089,103 +2076,10 @@ __global__ void __launch_bounds__(TR_BLK) k_trace_copy(const Msg* __restrict__ i
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) tot_out[0] = rank0;
 }
 
-// ------------------------------------------------------------- buffers --
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    // grow to the next power of two (per-round sizes peak on broadcast
-    // rounds; a 25 % step re-allocated -- 1 ms each -- for many rounds),
-    // contents not kept
-    // headroom: grow to the power of two at or above want * (1 + headroom / 4);
-    // headroom < 0: exactly want, rounded up to 64 MiB past 1 GiB (an
-    // up-front reservation sized against the free device memory)
-    int ensure(size_t want, int headroom = 0) {
-        if (want <= n) return PSIM_OK;
-        static const bool trace = getenv("PSIM_TRACE_GROW") != nullptr;
-        if (trace && want >= (1u << 20))
-            std::fprintf(stderr, "psim: grow %zu -> %zu (want) x %zu B\n", n, want, sizeof(T));
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        const size_t goal = want + want / 4 * (size_t)(headroom > 0 ? headroom : 0);
-        size_t cap = 1024;
-        while (cap < goal) cap <<= 1;
-        // past 1 GiB a power of two (or the caller's headroom) may waste up
-        // to half: 1/8 headroom in 64 MiB steps instead (at 2^26 nodes the
-        // message buffers are tens of GB)
-        if (headroom < 0) cap = want;
-        if (cap * sizeof(T) > (1ull << 30)) {
-            const size_t step = (64ull << 20) / sizeof(T);
-            cap = (want + (headroom < 0 ? 0 : want / 8) + step - 1) / step * step;
-        }
-        if (hipMalloc(&p, cap * sizeof(T)) != hipSuccess) {
-            size_t fr = 0, tot = 0;
-            (void)hipGetLastError();
-            if (hipMemGetInfo(&fr, &tot) == hipSuccess)
-                std::fprintf(stderr, "psim: device allocation of %.2f GB failed (%.2f of %.2f GB free)\n",
-                             cap * sizeof(T) / 1e9, fr / 1e9, tot / 1e9);
-            p = nullptr;
-            return PSIM_ENOMEM;
-        }
-        n = cap;
-        return PSIM_OK;
-    }
-    // grow like ensure(), keeping the first `keep` elements (copied on `st`)
-    int ensure_keep(size_t want, size_t keep, hipStream_t st) {
-        if (want <= n) return PSIM_OK;
-        if (!p || !keep) return ensure(want);
-        DBuf<T> nb;
-        TRY(nb.ensure(want));
-        if (hipMemcpyAsync(nb.p, p, std::min(keep, n) * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-            nb.release();
-            return PSIM_EDEVICE;
-        }
-        release();
-        p = nb.p; n = nb.n;
-        return PSIM_OK;
-    }
-    int alloc(size_t want) {    // exact, zeroed
-        static const bool trace = getenv("PSIM_TRACE_GROW") != nullptr;
-        if (trace && want >= (1u << 20)) std::fprintf(stderr, "psim: alloc %zu x %zu B\n", want, sizeof(T));
-        if (hipMalloc(&p, std::max<size_t>(want, 1) * sizeof(T)) != hipSuccess) return PSIM_ENOMEM;
-        n = want;
-        if (hipMemset(p, 0, std::max<size_t>(want, 1) * sizeof(T)) != hipSuccess) return PSIM_EDEVICE;
-        return PSIM_OK;
-    }
-    // exact, zeroed on `st` (ordered before the stream's later kernels; the
-    // null-stream fill of alloc() is not ordered with a non-blocking stream)
-    int alloc_on(size_t want, hipStream_t st) {
-        if (hipMalloc(&p, std::max<size_t>(want, 1) * sizeof(T)) != hipSuccess) return PSIM_ENOMEM;
-        n = want;
-        if (hipMemsetAsync(p, 0, std::max<size_t>(want, 1) * sizeof(T), st) != hipSuccess) return PSIM_EDEVICE;
-        return PSIM_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
-// a temporary device buffer, released on every return path
-template <typename T>
-struct TmpBuf : DBuf<T> {
-    TmpBuf() = default;
-    TmpBuf(const TmpBuf&) = delete;
-    TmpBuf& operator=(const TmpBuf&) = delete;
-    ~TmpBuf() { this->release(); }
-};
-
-enum Kern { KT_EVENTS, KT_PREPARE, KT_CONSUME, KT_SCAN, KT_COMPACT, KT_SORT, KT_EXCHANGE, KT_GATHER,
-            KT_STATS, KT_HOST_EXPORT, KT_HOST_IMPORT, KT_PACK, KT_TRACE_COUNT, KT_TRACE_COPY, KT_N };
+// ------------ host side (the buffers, Shard and psim_handle: psim_host.h) --
 const char* kKernName[KT_N] = {"events", "prepare", "consume", "scan", "compact", "sort",
                                "exchange", "gather", "stats", "k_host_export", "k_host_import", "pay_pack",
                                "k_trace_count", "k_trace_copy"};
-
-inline uint32_t grid_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + BLK - 1) / BLK); }
-
-int bits_for(uint64_t n) {
-    int b = 1;
-    while (b < 32 && (1ull << b) < n) b++;
-    return b;
-}
 
 // Up-front reservations (the first round of a handle): a buffer that grows
 // mid-run is a hipFree + hipMalloc, and the driver clears fresh device memory
@@ -3201,223 +2095,6 @@ constexpr uint64_t RCAP_PER_NODE = 4;       // initial route capacity (records) 
 constexpr uint64_t RCAP_RESERVE = 8;        // ... reserved up front where it fits
 constexpr double RCAP_FREE_FRAC = 0.30;
 constexpr double OUTBOX_SPARE = 0.12;
-
-struct Shard {
-    uint32_t idx = 0, lo = 0, n = 0;    // global shard index, owned [lo, lo + n)
-    hipStream_t stream = nullptr;
-    // replicated (global id)
-    DBuf<uint8_t> flags, part;
-    DBuf<upart_t> upart;                // k_node_prep's up-and-partition pairs (RoundArgs::upart)
-    DBuf<uint16_t> lite_cm;             // k_relay's connection bits and emitted counts of lite-list nodes (RoundArgs::lite_cm)
-    DBuf<uint32_t> crash_bits;   // RoundArgs::crash_bits
-    DBuf<uint8_t> btab;          // RoundArgs::btab (psim_set_bucket_table), global id
-    // local rows
-    DBuf<Hdr> hdr;
-    DBuf<uint32_t> act, pas, pt_all, pt_com, pt_eag, pt_laz, pt_rt, start;
-    DBuf<uint64_t> sentm, recvm, mapx;  // id maps (id << 32 | peer): own rows, extension rows (pool)
-    DBuf<uint32_t> mapx_top;
-    DBuf<uint32_t> origin;              // per local node: msg id + 1 it originates this round
-    DBuf<uint32_t> slots;               // the message slots (msg ids, then roots), a copy of the host's
-    DBuf<uint32_t> bc_roots, bc_msgs;   // this round's broadcasts
-    DBuf<uint64_t> pt_out, outx;        // outstanding: own rows, extension rows (pool)
-    DBuf<uint32_t> conn;                // connection tables (PSIM_CONN_CAP per node; HyParView)
-    DBuf<uint32_t> outx_top;
-    // inbox of the next round: sorted (local dst | bound, record index) pairs
-    DBuf<uint32_t> ikeys, ivals;
-    uint32_t m_in = 0;
-    DBuf<Msg> outbox;                   // this round's emissions (holes between node regions)
-    // G > 1: the received records in the wire format, in source-shard order:
-    // their heads, the long ones' tails, and per source its first head and
-    // first tail (wseg, 2 (G + 1) words; its host copy until the next round)
-    DBuf<Wire> recvh, recvt;
-    DBuf<uint32_t> wseg;
-    std::vector<uint32_t> wseg_host;
-    // records by node run, in inbox order: read by this round's node-round
-    // kernels, then (same stream) overwritten by the route with the next
-    // round's -- one buffer, nothing reads a round's inbox after its consume
-    DBuf<Msg> inbox;
-    // per-round scratch
-    DBuf<uint32_t> okey, ocnt, in_beg,
-        d_nact, n_slow, n_pt, n_shuf, n_lite, n_ptl, rank, tmp, hist, hoff;
-    DBuf<uint32_t> rtot, rbase;         // route: per bucket its record count, and its first pair
-    DBuf<uint32_t> gcnt;                // fused route: per bucket its record count (k_bucket_fill's atomics)
-    DBuf<unsigned long long> bmask;     // per local node: message slots of its BROADCAST records
-    DBuf<uint2> pairs;                  // route: (destination in bucket | class, source index)
-    DBuf<unsigned long long> cb;        // per local node: inbox count | bound sum << 32 (n + 1)
-    DBuf<unsigned long long> btot;      // this round's outbox total (k_node_prep)
-    DBuf<uint4> desc, desc_slow, desc_pt, desc_shuf, desc_lite, desc_ptl;   // work descriptors; those k_relay leaves to k_consume / k_pt / k_shuf
-    DBuf<uint64_t> bound, pscan, obase, stat_part, stat_out, stat_tile, d_off;   // bound: packed (bound << 32 | work)
-    DBuf<uint8_t> cub_tmp;              // the scan's tile totals
-    DBuf<uint32_t> ev_ids, ev_contacts, stop_ids, n_stop;
-    bool tomb_live = false;             // full: snapshots carry their remove rows
-    DBuf<Wire> sendbuf;                 // G > 1: the outbox in the wire format, by owner (k_owner_part)
-    // pluggable manager
-    DBuf<uint32_t> sview, sinv, fbits, pay[2], pay_top;
-    int pay_cur = 0;
-    // full, G > 1 (the payload exchange): the (owner, slot) bitmap and its
-    // popcount scan, the per-owner row counts (device, then host), the slot
-    // of every row sent and the rows packed by owner, and the rows other
-    // shards shipped for the next round's
-    // records -- imp_rows of them in source-shard order, fw words each, 2 fw
-    // once tomb_live
-    DBuf<uint32_t> pbits, prank, plist, paysend, pay_imp;
-    DBuf<uint64_t> pcnt_d;
-    std::vector<uint64_t> pcnt;
-    uint32_t pbw = 0, imp_rows = 0;
-    DBuf<uint8_t> faulted;              // omission faults: generally omitting nodes (global id)
-    DBuf<uint64_t> omit;                // ... sorted send-omission pairs, then receive-omission pairs
-    // per destination shard: the send buffer's offsets (2 G + 1: heads of
-    // each owner, tails of each owner, the end), heads and tails sent
-    std::vector<uint64_t> soff, scnt, lcnt;
-    uint32_t pper = BLK;               // k_node_prep / k_desc: nodes per block (a multiple of BLK)
-    uint32_t pgrid = 0, cgrid = 0, rgrid = 0, tgrid = 0, sgrid = 0, lgrid = 0, qgrid = 0, egrid = 0;   // stats rows: prepare,
-                                   // consume, relay, plumtree, shuffle-start, lite, Plumtree-lane blocks
-    // pinned host words: NST stats and the consume span (stat_out), then the
-    // outbox total and the routed record count: the round's two read-backs
-    uint64_t* pin = nullptr;
-    uint64_t* pin_dev = nullptr;        // the same words, as the kernels store them
-    // phase timers: event pairs recorded on the stream and read back once per
-    // round, after the round's final synchronisation (no sync per phase)
-    static constexpr int MAXT = 32;
-    hipEvent_t ev[MAXT][2];
-    int tk[MAXT];
-    int tn = 0;
-    hipEvent_t wait_ev = nullptr;
-    // the three HyParView kernels after k_relay take disjoint node lists and
-    // run concurrently: k_shuf and k_consume on two side streams forked from
-    // and joined back into `stream` (fork_ev, join_ev)
-    hipStream_t side[2] = {nullptr, nullptr};
-    hipEvent_t fork_ev = nullptr, join_ev[2] = {nullptr, nullptr};
-    bool ev_live = false;
-    bool reserved = false;              // first-round capacity reservation done
-    bool upart_valid = false;           // upart holds this state's pairs (RoundArgs::upart_dirty)
-    uint64_t rcap = 0;                  // records the route's buffers hold (G == 1: checked on the device)
-    // batches of rounds without host waits (run_batch): the abort word
-    // (code, round) in device memory; while a batch is enqueued, k_desc
-    // checks the outbox against desc_cap and the route flags its overflow
-    // for round batch_round1 - 1; round j's stats go to pinned slot j + 1
-    DBuf<uint32_t> ctl;
-    uint64_t desc_cap = 0;
-    uint32_t batch_round1 = 0;
-    uint32_t stat_slot = 0;
-    // a batch's route prepares the next round (RoutePrep, PSIM_PREP_FUSED):
-    // prep_next = that round + 1 while its route is enqueued (0: no), and
-    // prepared = the round being enqueued was prepared by the last route
-    uint32_t prep_next = 0;
-    bool prepared = false;
-    bool outx_short = false;            // the outstanding pool failed to grow (reported once per shard)
-    // the rank path's batches (run_batch_ranked): the fixed per-owner
-    // capacities of the exchange (heads, tails; 0 = not known yet: no batch),
-    // identical on every rank (set from all-reduced counts), and the next
-    // batch's length (1 after an abort, doubling up to BATCH_MAX)
-    uint32_t xcap_h = 0, xcap_t = 0;
-    uint32_t xbatch = 1;
-    uint64_t trace_tmax = 0, trace_mmax = 0;   // PSIM_TRACE_BOUND's high-water marks
-    // the message trace (psim_trace_watch; none of it allocated on an unarmed
-    // handle): the watch bitmap (global ids; none when every node is
-    // watched), the kept records with their rounds, the shard's matches since
-    // the last read (two words, swapped every captured round: tr_cur names
-    // the current one; the first `capacity` of them are kept), and a round's
-    // scratch (block counts, group ballots)
-    DBuf<uint32_t> tr_bits, tr_round, tr_cnt;
-    DBuf<Msg> tr_rec;
-    DBuf<unsigned long long> tr_tot, tr_ballot;
-    int tr_cur = 0;
-};
-
-// the events a handle holds for its next round (psim_handle's pend_* members)
-struct PendingEvents {
-    std::vector<uint32_t> crash, join, contact, lv_a, lv_t, b_root, b_msg;
-    std::vector<uint8_t> join_mark, part;
-    bool part_set = false, part_clear = false, faults_dirty = false;
-};
-
-}  // namespace
-
-struct psim_handle {
-    psim_config cfg;
-    uint32_t N = 0, G = 1, per = 0;
-    int device = 0;
-    uint32_t consume_blocks = 1024;     // resident k_consume blocks on the device
-    uint32_t pt_blocks = 1024;          // ... and k_pt blocks
-    uint32_t lite_blocks = 1024;        // the cap of the lite kernel's grid
-    // the lite list's kernel, chosen in psim_create: k_lite_quarter, four
-    // nodes per wave (psim_lite.hip); PSIM_LITE_HALF=1 keeps k_lite_half
-    // (two), PSIM_LITE_WAVE=1 the wave-per-node k_consume_lite (A/B)
-    psim::LiteKernel lite = {};
-    uint32_t ptl_blocks = 1024;         // ... and k_ptl blocks
-    uint64_t round = 0;
-    // a round failed half-way (psim_step returned an error from inside a
-    // round or batch): the state is not a round boundary any more, so every
-    // later psim_step answers PSIM_ESTATE instead of running on it
-    bool failed = false;
-    std::vector<Shard*> shards;         // shards owned by this process
-    int rank = 0, world = 1;
-    // the rank path (one shard per rank, the owner partition, the exchange
-    // and the collectives of psim_comm.h): world > 1, or a one-rank world
-    // whose cfg.comm_id was given (the 1-GPU diagnostic of the RCCL path:
-    // every collective, the self send/recv included, runs through the library)
-    bool ranked = false;
-    Comm* comm = nullptr;               // ranked: RCCL (or the loopback test vehicle), psim_comm.h
-    DBuf<uint64_t> comm_cnt;            // RCCL: [send counts | recv counts]
-    // a host-exchange handle (cfg.comm_id from psim_host_comm_id): one shard,
-    // the range [lo, hi) of the id space; the host speaks for every other id.
-    // G = 3 owner classes (below, owned, at or above), the shard is class 1;
-    // a round is psim_round_emit .. psim_round_absorb (round_open between)
-    bool hosted = false, round_open = false;
-    std::vector<Msg> host_out, host_in; // the open round's outbound records; the absorbed ones, sorted
-    std::vector<uint32_t> host_wbase;   // k_host_import: the long records before each wave's
-    DBuf<Msg> hx_rec;                   // the dense records on the device (export, then import)
-    DBuf<uint32_t> hx_wbase;
-    PendingEvents open_ev;              // the events queued while the round is open (pending_swap)
-    // the exchange since creation (psim_get_exchange_stats): records sent to
-    // another shard, and their wire bytes (heads + tails)
-    uint64_t x_records = 0, x_bytes = 0;
-    // pending events
-    std::vector<uint32_t> pend_crash, pend_join, pend_contact;
-    std::vector<uint8_t> pend_join_mark;   // ids in pend_join (a node starts at most once per round)
-    std::vector<uint32_t> pend_lv_a, pend_lv_t;     // leave/1 calls: actor, target
-    std::vector<uint8_t> pend_part;
-    bool pend_part_set = false, pend_part_clear = false;
-    std::vector<uint32_t> pend_b_root, pend_b_msg;    // broadcasts of the next round, in call order
-    uint32_t slot_tab[2 * PSIM_MSG_SLOTS];            // slot k: msg id [k], root [PSIM_MSG_SLOTS + k]
-    uint32_t tracked_msg = PSIM_NONE;
-    bool btab = false;                  // psim_set_bucket_table: the shards' btab rows are in use
-    uint32_t btab_hash = 0;             // ... their FNV-1a | 1 (0 = the default table), in snapshots
-    uint32_t fw = 0;                    // full strategy: words per member row (adds; removes beside)
-    bool tomb = false;                  // full: an ORSet remove exists (leave/1): kernels read remove rows
-    std::vector<uint8_t> started;       // full strategy: ids ever started (no restarts)
-    // omission faults (pluggable): the next round's installed funs, edited by
-    // psim_set_omission / psim_set_faulted and uploaded when changed; the
-    // counts of the ones in force
-    std::set<uint64_t> nx_omit_s, nx_omit_r;
-    std::vector<uint8_t> nx_faulted;
-    size_t nx_nfaulted = 0;
-    bool faults_dirty = false;
-    uint32_t faults = 0, n_omit_s = 0, n_omit_r = 0;
-    double kt_ms[KT_N] = {0};
-    uint64_t kt_n[KT_N] = {0};
-    // per-phase event timers (PSIM_PHASE_TIMERS=1): each event pair puts a
-    // ~10 us bubble between kernels, so by default only k_consume is timed,
-    // from its in-kernel span (RoundArgs::ktime)
-    bool phase_timers = false;
-    // blocks of the route / owner-partition passes (RB_MAX_BLOCKS; a test
-    // hook, PSIM_ROUTE_BLOCKS, lowers it so small runs take several steps per block)
-    uint32_t rb_blocks = RB_BLOCKS;
-    uint32_t rr_reg = RR_REG;           // k_bucket_route: pairs a thread may hold (PSIM_ROUTE_REG=0: the array path)
-    // one shard's own outbox routed by the fused pass (k_bucket_fill) instead
-    // of k_bucket_hist + k_bucket_offsets + k_bucket_scatter
-    // (PSIM_ROUTE_FUSED=0: the four passes, for A/B; reroutes take them too)
-    bool route_fused = true;
-    // the message trace: a watch is armed (psim_step then runs single rounds
-    // and captures after each), every node watched, PSIM_TRACE_* directions,
-    // the type mask, records kept between two reads (per shard, and in all)
-    bool trace_on = false, trace_all = false;
-    uint32_t trace_dir = 0, trace_mask = 0;
-    size_t trace_cap = 0;
-};
-
-namespace {
 
 // one shard in this process and no rank path: the round's emissions are
 // grouped by destination in place (phase_route_local); otherwise they go
@@ -3579,121 +2256,6 @@ void flush_timers(psim_handle* h, Shard* s) {
         h->kt_n[s->tk[i]]++;
     }
     s->tn = 0;
-}
-
-// ------------------------------------------------ exclusive prefix sum --
-// Reduce-then-scan over tiles of SCAN_TILE elements (256 threads x 8
-// consecutive elements each): tile totals, one block scans the totals, each
-// tile scans itself from its total's prefix.  Three launches, the input read
-// twice (at 2^20 nodes: 8 MB per read, a few microseconds); a count that
-// fits one tile is one launch.
-constexpr uint32_t SCAN_ITEMS = 8, SCAN_TILE = BLK * SCAN_ITEMS;
-
-// exclusive scan of one value per thread across the block; returns the
-// block total in *total (every thread)
-template <typename T, uint32_t NT>
-__device__ T block_excl(T v, T* total) {
-    __shared__ T wsum[NT / 64];
-    const uint32_t l = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    T x = v;                                          // inclusive scan within the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d);
-        if (l >= (uint32_t)d) x += y;
-    }
-    if (l == 63) wsum[wv] = x;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < NT / 64; k++) {
-        base += k < wv ? wsum[k] : T(0);
-        tot += wsum[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-
-template <typename T, typename TI>
-__global__ void __launch_bounds__(BLK) k_scan_tiles(const TI* __restrict__ in, uint32_t n, T* __restrict__ sums) {
-    const size_t b0 = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    T v = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN_ITEMS; k++) v += b0 + k < n ? in[b0 + k] : T(0);
-    T tot;
-    (void)block_excl(v, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-// one block: exclusive scan of the nt tile totals in place -- each thread a
-// contiguous run of ceil(nt / BLK) of them, one block scan of the run sums
-// (a block scan per BLK chunk took 12.7 us for 4097 totals: 17 serial
-// barrier pairs).  Up to SUMS_LDS totals go through LDS, loaded and stored
-// coalesced (the runs read straight from memory were ceil(nt / BLK)
-// dependent strided loads a thread: 8.6 us for 4097 totals)
-constexpr uint32_t SUMS_LDS = 4096 + 2 * BLK;
-template <typename T>
-__global__ void __launch_bounds__(BLK) k_scan_sums(T* sums, uint32_t nt) {
-    __shared__ T buf[SUMS_LDS];
-    const bool lds = nt <= SUMS_LDS;                  // (uniform)
-    T* p = lds ? buf : sums;
-    if (lds) {
-        for (uint32_t i = threadIdx.x; i < nt; i += BLK) buf[i] = sums[i];
-        __syncthreads();
-    }
-    const uint32_t per = (nt + BLK - 1) / BLK, i0 = threadIdx.x * per, i1 = min(nt, i0 + per);
-    T v = 0;
-    for (uint32_t i = i0; i < i1; i++) v += p[i];
-    T tot;
-    T run = block_excl(v, &tot);
-    for (uint32_t i = i0; i < i1; i++) {
-        const T x = p[i];
-        p[i] = run;
-        run += x;
-    }
-    if (lds) {
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < nt; i += BLK) sums[i] = buf[i];
-    }
-}
-
-template <typename T, typename TI>
-__global__ void __launch_bounds__(BLK) k_scan_apply(const TI* __restrict__ in, T* __restrict__ out, uint32_t n,
-                                                   const T* __restrict__ sums) {
-    const size_t b0 = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    T x[SCAN_ITEMS], v = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN_ITEMS; k++) {
-        x[k] = b0 + k < n ? in[b0 + k] : T(0);
-        v += x[k];
-    }
-    T tot;
-    T run = block_excl(v, &tot) + (sums ? sums[blockIdx.x] : T(0));
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN_ITEMS; k++) {
-        if (b0 + k < n) out[b0 + k] = run;
-        run += x[k];
-    }
-}
-
-// (TI: the input's type where it is narrower than the sums', e.g. byte counts)
-template <typename T, typename TI>
-int scan_excl(Shard* s, const TI* in, T* out, uint32_t n) {
-    // (a single-pass decoupled look-back measured 1.5 % slower a step at
-    // 2^20, profiles/r03/p25: its device-coherent status loads cost more than
-    // the two launches it saves; removed in round 4)
-    const uint32_t nt = (uint32_t)(((uint64_t)n + SCAN_TILE - 1) / SCAN_TILE);
-    if (nt <= 1) {
-        k_scan_apply<T, TI><<<1, BLK, 0, s->stream>>>(in, out, n, nullptr);
-    } else {
-        TRY(s->cub_tmp.ensure((size_t)nt * sizeof(T)));
-        T* sums = reinterpret_cast<T*>(s->cub_tmp.p);
-        k_scan_tiles<T, TI><<<nt, BLK, 0, s->stream>>>(in, n, sums);
-        k_scan_sums<T><<<1, BLK, 0, s->stream>>>(sums, nt);
-        k_scan_apply<T, TI><<<nt, BLK, 0, s->stream>>>(in, out, n, sums);
-    }
-    HIP_TRY(hipGetLastError());
-    return PSIM_OK;
 }
 
 // prepare's scan + descriptors: k_node_prep left its blocks' range sums in
@@ -6074,12 +4636,6 @@ static uint64_t members_hash(const uint32_t* row, uint32_t words) {
     return x;
 }
 
-static Shard* owner_of(psim_handle* h, uint32_t id) {
-    for (Shard* c : h->shards)
-        if (id >= c->lo && id < c->lo + c->n) return c;
-    return nullptr;
-}
-
 int psim_get_strategy_nodes(psim_handle* h, uint32_t first, uint32_t count, psim_strategy_view* out) {
     if (!h || (count && !out)) return PSIM_EINVAL;
     if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE || h->round_open) return PSIM_ESTATE;
@@ -6188,619 +4744,6 @@ int psim_get_delivery(psim_handle* h, uint32_t first, uint32_t count, uint8_t* h
     }
     return PSIM_OK;
 }
-
-// weakly connected components of the live nodes over the rows k_cc_hook
-// reads: label propagation to a fixed point, then the component count and the
-// largest (comps, largest: zeroed device words; L, size: n words, size zeroed)
-static int cc_run(const uint32_t* off, const uint8_t* rn, const uint32_t* adj, const uint8_t* fl, uint32_t n,
-                  uint32_t* L, uint32_t* size, uint32_t* flag, unsigned long long* comps,
-                  unsigned long long* largest, hipStream_t st) {
-    k_cc_init<<<grid_for(n), BLK, 0, st>>>(fl, n, L);
-    for (int it = 0; it < 4096; it++) {
-        uint32_t changed = 0;
-        HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
-        k_cc_hook<<<grid_for(n), BLK, 0, st>>>(off, rn, adj, fl, n, L, flag);
-        k_cc_jump<<<grid_for(n), BLK, 0, st>>>(n, L);
-        HIP_TRY(hipMemcpyAsync(&changed, flag, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (!changed) break;
-    }
-    k_cc_count<<<grid_for(n), BLK, 0, st>>>(L, n, size, comps);
-    k_cc_max<<<grid_for(n), BLK, 0, st>>>(size, n, largest);
-    HIP_TRY(hipGetLastError());
-    return PSIM_OK;
-}
-
-// the whole overlay's active rows by global id, gact (PSIM_ACTIVE_CAP ids a
-// row) and gan (their lengths), of per * G rows: the shards' rows are gathered
-// (device copies for virtual shards, an in-place ncclAllGather of equal
-// per-rank slots for RCCL ranks; 33 B per node), and every process then runs
-// the same kernels over the whole overlay
-static int gather_active_rows(psim_handle* h, hipStream_t st, TmpBuf<uint32_t>& gact, TmpBuf<uint8_t>& gan) {
-    const uint32_t per = h->per;
-    const size_t npad = (size_t)per * h->G;
-    TRY(gact.alloc_on(npad * PSIM_ACTIVE_CAP, st)); TRY(gan.alloc_on(npad, st));
-    for (Shard* s : h->shards)
-        if (s->n)
-            k_pack_act<<<grid_for(s->n), BLK, 0, st>>>(s->hdr.p, s->act.p, s->n,
-                                                       gact.p + (size_t)s->lo * PSIM_ACTIVE_CAP, gan.p + s->lo);
-    if (h->ranked) {
-        const size_t off = (size_t)h->rank * per;
-        TRY(h->comm->all_gather(gact.p + off * PSIM_ACTIVE_CAP, gact.p, (size_t)per * PSIM_ACTIVE_CAP * 4, st));
-        TRY(h->comm->all_gather(gan.p + off, gan.p, per, st));
-    }
-    return PSIM_OK;
-}
-
-int psim_get_histograms(psim_handle* h, psim_histograms* out) {
-    if (!h || !out) return PSIM_EINVAL;
-    if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE || h->hosted) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
-    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
-    memset(out, 0, sizeof *out);
-    Shard* s0 = h->shards[0];
-    hipStream_t st = s0->stream;
-    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
-    const size_t N = h->N;
-    TmpBuf<uint32_t> ind;                        // in-degrees, active then passive, by global id
-    TmpBuf<unsigned long long> hist;
-    TRY(ind.alloc_on(2 * N, st));
-    TRY(hist.alloc_on(H_N + 4, st));
-    const uint64_t tbit = h->tracked_msg == PSIM_NONE ? 0ull : 1ull << (h->tracked_msg % PSIM_MSG_SLOTS);
-    for (Shard* s : h->shards)
-        k_hist_out<<<grid_for(s->n), BLK, 0, st>>>(s->hdr.p, s->act.p, s->pas.p, s->flags.p, s->lo, s->n, tbit,
-                                                   ind.p, ind.p + N, hist.p);
-    if (h->ranked) {
-        TRY(h->comm->all_reduce(ind.p, 2 * N, CType::U32, COp::SUM, st));
-    }
-    for (Shard* s : h->shards)
-        k_hist_in<<<grid_for(s->n), BLK, 0, st>>>(ind.p, ind.p + N, s->flags.p, s->lo, s->n, hist.p);
-    std::vector<unsigned long long> hv(H_N + 4, 0);
-    HIP_TRY(hipMemcpyAsync(hv.data(), hist.p, (H_N + 4) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (h->ranked) {                             // sums over ranks; the latest round: max
-        hv[H_N] = hv[H_LAST];
-        TRY(h->comm_cnt.ensure(H_N + 4));
-        HIP_TRY(hipMemcpyAsync(h->comm_cnt.p, hv.data(), (H_N + 4) * 8, hipMemcpyHostToDevice, st));
-        TRY(h->comm->all_reduce(h->comm_cnt.p, H_N, CType::U64, COp::SUM, st));
-        TRY(h->comm->all_reduce(h->comm_cnt.p + H_N, 1, CType::U64, COp::MAX, st));
-        HIP_TRY(hipMemcpyAsync(hv.data(), h->comm_cnt.p, (H_N + 4) * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        hv[H_LAST] = hv[H_N];
-    }
-    for (int k = 0; k < PSIM_HIST_BINS; k++) {
-        out->active_in[k] = hv[H_AIN * PSIM_HIST_BINS + k];
-        out->passive_in[k] = hv[H_PIN * PSIM_HIST_BINS + k];
-        out->active_out[k] = hv[H_AOUT * PSIM_HIST_BINS + k];
-        out->passive_fill[k] = hv[H_PFILL * PSIM_HIST_BINS + k];
-        out->hop[k] = hv[H_HOP * PSIM_HIST_BINS + k];
-    }
-    out->n_up = hv[H_NUP]; out->delivered = hv[H_DELIV]; out->last_round = hv[H_LAST];
-    out->active_links = hv[H_LINKS];
-    {
-        // symmetry and components need every node's active row
-        const uint32_t n = h->N;
-        TmpBuf<uint32_t> gact, L, sz, flag;
-        TmpBuf<uint8_t> gan;
-        TmpBuf<unsigned long long> r;
-        TRY(gather_active_rows(h, st, gact, gan));
-        const uint8_t* fl = s0->flags.p;         // replicated: every shard holds all N
-        TRY(L.alloc_on(n, st)); TRY(sz.alloc_on(n, st)); TRY(flag.alloc_on(1, st)); TRY(r.alloc_on(3, st));
-        k_hist_sym<<<grid_for(n), BLK, 0, st>>>(gan.p, gact.p, fl, n, r.p);
-        TRY(cc_run(nullptr, gan.p, gact.p, fl, n, L.p, sz.p, flag.p, r.p + 1, r.p + 2, st));
-        unsigned long long rv[3];
-        HIP_TRY(hipMemcpyAsync(rv, r.p, sizeof rv, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        out->symmetric_links = rv[0]; out->components = rv[1]; out->largest_component = rv[2];
-    }
-    return PSIM_OK;
-}
-
-// the full strategy's statistics, over every shard of this process and, on
-// ranks, as a collective (every rank gets the same struct).  The flags are
-// replicated, so every shard finds the lowest live id itself; its row belongs
-// to one shard or rank -- a device pointer serves virtual shards, ranks
-// all-reduce the row (its owner's words, zeros elsewhere: the sum is the row).
-// The ranks' minimum is the maximum of the complement (Comm reduces SUM and MAX)
-static int strategy_hist_full(psim_handle* h, psim_strategy_histograms* out) {
-    Shard* s0 = h->shards[0];
-    hipStream_t st = s0->stream;                 // (the caller synchronised every shard's stream)
-    TmpBuf<unsigned long long> sf;
-    TmpBuf<uint32_t> low, ref;
-    TRY(sf.alloc_on(SF_N, st)); TRY(low.alloc_on(1, st));
-    HIP_TRY(hipMemsetAsync(sf.p + SF_MIN, 0xFF, 8, st));
-    HIP_TRY(hipMemsetAsync(low.p, 0xFF, 4, st));
-    k_sh_low<<<grid_for(h->N), BLK, 0, st>>>(s0->flags.p, 0, h->N, low.p);
-    HIP_TRY(hipGetLastError());
-    uint32_t lowest = PSIM_NONE;
-    HIP_TRY(hipMemcpyAsync(&lowest, low.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (lowest != PSIM_NONE) {
-        Shard* o = owner_of(h, lowest);
-        const uint32_t* rp = o ? o->fbits.p + (size_t)(lowest - o->lo) * 2 * h->fw : nullptr;
-        if (h->ranked && h->world > 1) {
-            TRY(ref.alloc_on(2 * h->fw, st));
-            if (rp) HIP_TRY(hipMemcpyAsync(ref.p, rp, 2 * h->fw * 4, hipMemcpyDeviceToDevice, st));
-            TRY(h->comm->all_reduce(ref.p, 2 * h->fw, CType::U32, COp::SUM, st));
-            rp = ref.p;
-        }
-        if (!rp) return PSIM_ESTATE;
-        for (Shard* s : h->shards)
-            if (s->n)
-                k_sh_full<<<grid_for((uint64_t)s->n * 64), BLK, 0, st>>>(s->fbits.p, s->flags.p, s->lo, s->n, h->fw,
-                                                                       h->tomb ? 1u : 0u, rp, sf.p);
-        HIP_TRY(hipGetLastError());
-    }
-    unsigned long long v[SF_N];
-    HIP_TRY(hipMemcpyAsync(v, sf.p, sizeof v, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (h->ranked && h->world > 1) {
-        // (a rank without live nodes: SF_MIN is still all ones, its complement 0)
-        uint64_t w[SF_N] = {v[SF_NUP], v[SF_SUM], v[SF_AGREE], v[SF_MAX], ~(uint64_t)v[SF_MIN]};
-        TRY(h->comm_cnt.ensure(SF_N));
-        HIP_TRY(hipMemcpyAsync(h->comm_cnt.p, w, sizeof w, hipMemcpyHostToDevice, st));
-        TRY(h->comm->all_reduce(h->comm_cnt.p, 3, CType::U64, COp::SUM, st));
-        TRY(h->comm->all_reduce(h->comm_cnt.p + 3, 2, CType::U64, COp::MAX, st));
-        HIP_TRY(hipMemcpyAsync(w, h->comm_cnt.p, sizeof w, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        v[SF_NUP] = w[0]; v[SF_SUM] = w[1]; v[SF_AGREE] = w[2]; v[SF_MAX] = w[3]; v[SF_MIN] = ~w[4];
-    }
-    out->n_up = v[SF_NUP];
-    if (v[SF_NUP]) {
-        out->members_min = v[SF_MIN]; out->members_max = v[SF_MAX]; out->members_sum = v[SF_SUM];
-        out->agreeing = v[SF_AGREE];
-    }
-    return PSIM_OK;
-}
-
-// the compact CSR of a SCAMP handle's overlay, the same on every rank: node
-// i's cnt[i] links at adj + off[i] (ids by equal per-shard slots, per * G of
-// them; the pad ids hold no links)
-struct ShCsr {
-    TmpBuf<uint8_t> cnt;
-    TmpBuf<uint32_t> off, base, adj;
-    TmpBuf<unsigned long long> tot;
-};
-// the counts and offsets of a CSR, zeroed, before its count pass
-static int csr_alloc(psim_handle* h, hipStream_t st, ShCsr& c) {
-    const size_t npad = (size_t)h->per * h->G;
-    TRY(c.tot.alloc_on(1, st));
-    TRY(c.cnt.alloc_on(npad + 1, st)); TRY(c.off.alloc_on(npad + 1, st));
-    TRY(c.base.alloc_on(h->ranked ? (uint32_t)h->world : 1u, st));
-    return PSIM_OK;
-}
-// after the count pass wrote this process's counts: every rank's counts, the
-// row offsets and the (empty) links.  slot: the links of a rank's share
-static int csr_place(psim_handle* h, hipStream_t st, ShCsr& c, uint32_t& slot) {
-    const uint32_t per = h->per, npad = per * h->G;
-    const uint32_t W = h->ranked ? (uint32_t)h->world : 1u, rper = h->ranked ? per : npad;
-    if (h->ranked) TRY(h->comm->all_gather(c.cnt.p + (size_t)h->rank * per, c.cnt.p, per, st));
-    // row offsets: a scan of all counts (entry npad: the total); a rank's
-    // rows are packed from the start of its slot, every slot as long as the
-    // largest rank's links, so the gathered CSR is the same everywhere
-    TRY(scan_excl(h->shards[0], c.cnt.p, c.off.p, npad + 1));
-    k_sh_rank_tot<<<1, 64, 0, st>>>(c.off.p, rper, W, npad, c.base.p, c.tot.p);
-    unsigned long long slot64 = 0;
-    HIP_TRY(hipMemcpyAsync(&slot64, c.tot.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (slot64 * W > 0xFFFFFFFFull) return PSIM_ENOMEM;       // (row offsets are 32-bit)
-    slot = (uint32_t)slot64;
-    if (W > 1) k_sh_shift<<<grid_for(npad), BLK, 0, st>>>(c.off.p, npad, rper, slot, c.base.p);
-    TRY(c.adj.alloc_on((size_t)slot * W, st));
-    return PSIM_OK;
-}
-// after the pack pass wrote this process's links: every rank's
-static int csr_gather(psim_handle* h, hipStream_t st, ShCsr& c, uint32_t slot) {
-    if (h->ranked && slot) TRY(h->comm->all_gather(c.adj.p + (size_t)h->rank * slot, c.adj.p, (size_t)slot * 4, st));
-    return PSIM_OK;
-}
-
-// sl: the SL_N words the count pass adds its per-node statistics to
-static int sh_build_csr(psim_handle* h, hipStream_t st, unsigned long long* sl, ShCsr& c) {
-    const uint8_t* fl = h->shards[0]->flags.p;   // replicated: every shard holds all N
-    const uint32_t N = h->N, v2 = h->cfg.strategy == PSIM_STRATEGY_SCAMP_V2 ? 1u : 0u;
-    auto rows_grid = [](uint32_t n) { return (n + SH_NPB - 1) / SH_NPB; };
-    TRY(csr_alloc(h, st, c));
-    // 1. the row pass: per-node statistics, and the link count of every node
-    for (Shard* s : h->shards)
-        if (s->n)
-            k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, c.cnt.p, nullptr,
-                                                       nullptr, sl);
-    HIP_TRY(hipGetLastError());
-    // 2. row offsets, then the pack pass
-    uint32_t slot = 0;
-    TRY(csr_place(h, st, c, slot));
-    for (Shard* s : h->shards)
-        if (s->n)
-            k_sh_rows<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sview.p, fl, s->lo, s->n, N, v2, c.cnt.p, c.off.p,
-                                                       c.adj.p, sl);
-    HIP_TRY(hipGetLastError());
-    return csr_gather(h, st, c, slot);
-}
-
-int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) {
-    if (!h || !out) return PSIM_EINVAL;
-    if (h->cfg.manager != PSIM_MANAGER_PLUGGABLE || h->hosted) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
-    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
-    memset(out, 0, sizeof *out);
-    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
-    if (h->cfg.strategy == PSIM_STRATEGY_FULL) return strategy_hist_full(h, out);
-    Shard* s0 = h->shards[0];
-    hipStream_t st = s0->stream;
-    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
-    const uint32_t N = h->N, v2 = h->cfg.strategy == PSIM_STRATEGY_SCAMP_V2 ? 1u : 0u;
-    auto rows_grid = [](uint32_t n) { return (n + SH_NPB - 1) / SH_NPB; };
-    // temporaries: O(N) bytes and words, and the links
-    TmpBuf<unsigned long long> sl, sg;
-    TmpBuf<uint32_t> indeg, L, sz, flag;
-    ShCsr csr;
-    TmpBuf<uint8_t>& cnt = csr.cnt;
-    TmpBuf<uint32_t>& off = csr.off, & adj = csr.adj;
-    TRY(sl.alloc_on(SL_N, st)); TRY(sg.alloc_on(SG_N, st));
-    // 1., 2. the row pass and the CSR
-    TRY(sh_build_csr(h, st, sl.p, csr));
-    // 3. over the whole CSR (every rank the same): in-degrees, reciprocity,
-    // components; the in_view rows are local and probe it
-    TRY(indeg.alloc_on(N, st)); TRY(L.alloc_on(N, st)); TRY(sz.alloc_on(N, st)); TRY(flag.alloc_on(1, st));
-    k_sh_links<<<grid_for(N), BLK, 0, st>>>(off.p, cnt.p, adj.p, N, indeg.p, sg.p);
-    k_sh_in<<<grid_for(N), BLK, 0, st>>>(indeg.p, cnt.p, fl, N, sg.p);
-    if (v2)
-        for (Shard* s : h->shards)
-            if (s->n)
-                k_sh_inv<<<rows_grid(s->n), BLK, 0, st>>>(s->hdr.p, s->sinv.p, fl, s->lo, s->n, N, off.p, cnt.p,
-                                                          adj.p, sl.p);
-    HIP_TRY(hipGetLastError());
-    TRY(cc_run(off.p, cnt.p, adj.p, fl, N, L.p, sz.p, flag.p, sg.p + SG_COMPS, sg.p + SG_LARGEST, st));
-    if (h->ranked) {                             // the local sums over ranks; the longest view: max
-        TRY(h->comm->all_reduce(sl.p, SL_VMAX, CType::U64, COp::SUM, st));
-        TRY(h->comm->all_reduce(sl.p + SL_VMAX, 1, CType::U64, COp::MAX, st));
-    }
-    unsigned long long lv[SL_N], gv[SG_N];
-    HIP_TRY(hipMemcpyAsync(lv, sl.p, sizeof lv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(gv, sg.p, sizeof gv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int k = 0; k < PSIM_HIST_BINS; k++) {
-        out->view_fill[k] = lv[SL_VFILL * PSIM_HIST_BINS + k];
-        out->in_fill[k] = lv[SL_IFILL * PSIM_HIST_BINS + k];
-        out->out_degree[k] = lv[SL_OUT * PSIM_HIST_BINS + k];
-        out->in_degree[k] = gv[k];
-    }
-    out->n_up = lv[SL_NUP]; out->view_sum = lv[SL_VSUM]; out->in_sum = lv[SL_ISUM]; out->view_max = lv[SL_VMAX];
-    out->dangling_links = lv[SL_DANG]; out->self_entries = lv[SL_SELF]; out->duplicate_entries = lv[SL_DUP];
-    out->in_view_links = lv[SL_IVL]; out->in_view_confirmed = lv[SL_IVC];
-    out->links = gv[SG_LINKS]; out->mutual_links = gv[SG_MUTUAL]; out->in_degree_max = gv[SG_INMAX];
-    out->isolated = gv[SG_ISOL]; out->components = gv[SG_COMPS]; out->largest_component = gv[SG_LARGEST];
-    return PSIM_OK;
-}
-
-int psim_get_graph_metrics(psim_handle* h, const uint32_t* sources, size_t n_sources, uint32_t max_levels,
-                           psim_graph_metrics* out) {
-    static_assert(PSIM_GRAPH_SOURCES == 64, "one bit of a 64-bit word per source slot");
-    if (!h || !out || (n_sources && !sources) || n_sources > PSIM_GRAPH_SOURCES) return PSIM_EINVAL;
-    const bool pl = h->cfg.manager == PSIM_MANAGER_PLUGGABLE;
-    if (h->hosted || (pl && h->cfg.strategy == PSIM_STRATEGY_FULL)) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
-    if (h->round_open) return PSIM_ESTATE;
-    const uint32_t N = h->N, ns = (uint32_t)n_sources;
-    uint32_t src[PSIM_GRAPH_SOURCES] = {0};
-    for (uint32_t j = 0; j < ns; j++) {
-        if (sources[j] >= N) return PSIM_ERANGE;
-        src[j] = sources[j];
-    }
-    for (uint32_t j = 0; j < ns; j++)
-        for (uint32_t q = 0; q < j; q++)
-            if (src[q] == src[j]) return PSIM_EINVAL;
-    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
-    memset(out, 0, sizeof *out);
-    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
-    Shard* s0 = h->shards[0];
-    hipStream_t st = s0->stream;
-    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
-    // 1. the link set as rows, the same on every rank: the SCAMP CSR, or
-    // HyParView's gathered rows filtered once (p != i, p live), so that both
-    // halves read the same L
-    ShCsr csr;
-    TmpBuf<unsigned long long> sl, gm;
-    TmpBuf<uint32_t> gact, fadj;
-    TmpBuf<uint8_t> gan, fcnt;
-    const uint32_t* off = nullptr;
-    const uint32_t* adj = nullptr;
-    const uint8_t* cnt = nullptr;
-    TRY(gm.alloc_on(GM_N, st));
-    if (pl) {
-        TRY(sl.alloc_on(SL_N, st));              // (the count pass's statistics: not reported here)
-        TRY(sh_build_csr(h, st, sl.p, csr));
-        off = csr.off.p; adj = csr.adj.p; cnt = csr.cnt.p;
-    } else {
-        TRY(gather_active_rows(h, st, gact, gan));
-        TRY(fadj.alloc_on((size_t)N * PSIM_ACTIVE_CAP, st)); TRY(fcnt.alloc_on(N, st));
-        k_gm_filter<<<grid_for(N), BLK, 0, st>>>(gan.p, gact.p, fl, N, fadj.p, fcnt.p);
-        adj = fadj.p; cnt = fcnt.p;
-    }
-    // 2. clustering
-    if (pl) k_gm_cluster<<<(N + BLK / 64 - 1) / (BLK / 64), BLK, 0, st>>>(off, cnt, adj, fl, N, gm.p);
-    else k_gm_cluster_hv<<<grid_for((uint64_t)N * PSIM_ACTIVE_CAP), BLK, 0, st>>>(cnt, adj, fl, N, gm.p);
-    HIP_TRY(hipGetLastError());
-    unsigned long long gv[GM_N];
-    HIP_TRY(hipMemcpyAsync(gv, gm.p, sizeof gv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    out->n_up = gv[GM_NUP]; out->links = gv[GM_LINKS]; out->cl_nodes = gv[GM_NODES];
-    out->cl_closed = gv[GM_CLOSED]; out->cl_pairs = gv[GM_PAIRS]; out->cl_sum_q32 = gv[GM_Q32];
-    if (!ns) return PSIM_OK;
-    // 3. the BFS: a push and a level kernel per level, the level's words read
-    // back after each (zero new bits end it), at most `cap` levels
-    const uint32_t cap = !max_levels || max_levels > PSIM_GRAPH_MAX_LEVELS ? PSIM_GRAPH_MAX_LEVELS : max_levels;
-    TmpBuf<uint32_t> dsrc;
-    TmpBuf<unsigned long long> seen, front, next, lv, reach;
-    TRY(dsrc.alloc_on(PSIM_GRAPH_SOURCES, st));
-    TRY(seen.alloc_on(N, st)); TRY(front.alloc_on(N, st)); TRY(next.alloc_on(N, st));
-    TRY(lv.alloc_on(2 * ((size_t)cap + 1), st)); TRY(reach.alloc_on(PSIM_GRAPH_SOURCES, st));
-    HIP_TRY(hipMemcpyAsync(dsrc.p, src, sizeof src, hipMemcpyHostToDevice, st));
-    k_gm_init<<<1, 64, 0, st>>>(dsrc.p, ns, fl, seen.p, front.p, lv.p);      // (lv[0]: the live slots)
-    unsigned long long live = 0;
-    HIP_TRY(hipMemcpyAsync(&live, lv.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    out->sources_live = (uint64_t)__builtin_popcountll(live);
-    if (!live) return PSIM_OK;
-    for (uint32_t d = 1; d <= cap; d++) {
-        unsigned long long w[2] = {0, 0};
-        k_gm_push<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, N, front.p, seen.p, next.p);
-        k_gm_level<<<grid_for(N), BLK, 0, st>>>(N, next.p, seen.p, front.p, lv.p + 2 * (size_t)d, reach.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(w, lv.p + 2 * (size_t)d, sizeof w, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        out->levels = d;
-        if (!w[0]) break;
-        out->dist[d < PSIM_HIST_BINS ? d : PSIM_HIST_BINS - 1] += w[1];
-        out->dist_sum += (uint64_t)d * w[1];
-        out->pairs_reached += w[1];
-        for (uint32_t j = 0; j < PSIM_GRAPH_SOURCES; j++)
-            if ((w[0] >> j) & 1) out->ecc[j] = d;
-        out->ecc_max = d;
-        if (d == cap) out->truncated = 1;
-    }
-    unsigned long long rv[PSIM_GRAPH_SOURCES];
-    HIP_TRY(hipMemcpyAsync(rv, reach.p, sizeof rv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t j = 0; j < PSIM_GRAPH_SOURCES; j++) out->reach[j] = rv[j];
-    out->pairs_unreached = out->sources_live * (out->n_up - 1) - out->pairs_reached;
-    return PSIM_OK;
-}
-
-int psim_get_resilience(psim_handle* h, const psim_failure_case* cases, size_t n_cases, uint64_t fail_seed,
-                        uint32_t max_levels, psim_resilience* out) {
-    static_assert(PSIM_FAIL_CASES == 64 && PSIM_FAIL_CASES == PSIM_GRAPH_SOURCES,
-                  "one bit of k_gm_level's 64-bit word per case");
-    if (!h || !out || (n_cases && !cases) || n_cases > PSIM_FAIL_CASES) return PSIM_EINVAL;
-    const uint32_t nc = (uint32_t)n_cases;
-    for (uint32_t j = 0; j < nc; j++)
-        if (cases[j].reserved) return PSIM_EINVAL;
-    const bool pl = h->cfg.manager == PSIM_MANAGER_PLUGGABLE;
-    if (h->hosted || (pl && h->cfg.strategy == PSIM_STRATEGY_FULL)) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
-    if (h->round_open) return PSIM_ESTATE;
-    const uint32_t N = h->N;
-    for (uint32_t j = 0; j < nc; j++)
-        if (cases[j].source >= N) return PSIM_ERANGE;
-    // the case table: cases of one salt side by side (k_rs_alive)
-    uint32_t ord[PSIM_FAIL_CASES], par[RS_PAR] = {0};
-    for (uint32_t j = 0; j < nc; j++) ord[j] = j;
-    std::stable_sort(ord, ord + nc, [&](uint32_t a, uint32_t b) { return cases[a].salt < cases[b].salt; });
-    for (uint32_t q = 0; q < nc; q++) {
-        const psim_failure_case& c = cases[ord[q]];
-        par[RS_SRC + q] = c.source; par[RS_THR + q] = c.threshold; par[RS_SALT + q] = c.salt; par[RS_SLOT + q] = ord[q];
-    }
-    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
-    memset(out, 0, sizeof *out);
-    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
-    Shard* s0 = h->shards[0];
-    hipStream_t st = s0->stream;
-    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
-    // 1. the link set as rows, as psim_get_graph_metrics reads it
-    ShCsr csr;
-    TmpBuf<unsigned long long> sl, rs;
-    TmpBuf<uint32_t> gact, fadj, dpar;
-    TmpBuf<uint8_t> gan, fcnt;
-    const uint32_t* off = nullptr;
-    const uint32_t* adj = nullptr;
-    const uint8_t* cnt = nullptr;
-    if (pl) {
-        TRY(sl.alloc_on(SL_N, st));              // (the count pass's statistics: not reported here)
-        TRY(sh_build_csr(h, st, sl.p, csr));
-        off = csr.off.p; adj = csr.adj.p; cnt = csr.cnt.p;
-    } else {
-        TRY(gather_active_rows(h, st, gact, gan));
-        TRY(fadj.alloc_on((size_t)N * PSIM_ACTIVE_CAP, st)); TRY(fcnt.alloc_on(N, st));
-        k_gm_filter<<<grid_for(N), BLK, 0, st>>>(gan.p, gact.p, fl, N, fadj.p, fcnt.p);
-        adj = fadj.p; cnt = fcnt.p;
-    }
-    // 2. the survivor words (they seed the BFS) and the census
-    const uint32_t cap = !max_levels || max_levels > PSIM_GRAPH_MAX_LEVELS ? PSIM_GRAPH_MAX_LEVELS : max_levels;
-    TmpBuf<unsigned long long> alive, seen, front, next, lv, reach;
-    TRY(rs.alloc_on(RS_N, st)); TRY(dpar.alloc_on(RS_PAR, st));
-    TRY(alive.alloc_on(N, st)); TRY(seen.alloc_on(N, st)); TRY(front.alloc_on(N, st)); TRY(next.alloc_on(N, st));
-    HIP_TRY(hipMemcpyAsync(dpar.p, par, sizeof par, hipMemcpyHostToDevice, st));
-    k_rs_live<<<1, 64, 0, st>>>(dpar.p, nc, fl, rs.p);
-    k_rs_alive<<<grid_for(N), BLK, 0, st>>>(dpar.p, nc, fail_seed, fl, N, rs.p, alive.p, seen.p, front.p);
-    // (next: the in-link words until the BFS needs it zeroed again)
-    k_rs_census<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, fl, N, alive.p, next.p, rs.p);
-    if (nc) k_rs_sweep<<<grid_for(N), BLK, 0, st>>>(N, alive.p, next.p, rs.p);
-    HIP_TRY(hipGetLastError());
-    unsigned long long rv[RS_N];
-    HIP_TRY(hipMemcpyAsync(rv, rs.p, sizeof rv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    out->n_up = rv[RS_NUP]; out->links = rv[RS_L];
-    const unsigned long long live = rv[RS_LIVE];
-    out->live_mask = live; out->cases_live = (uint64_t)__builtin_popcountll(live);
-    for (uint32_t j = 0; j < PSIM_FAIL_CASES; j++) {
-        out->alive[j] = rv[RS_ALIVE + j]; out->links_alive[j] = rv[RS_LINKS + j];
-        out->no_out[j] = rv[RS_NOOUT + j]; out->no_in[j] = rv[RS_NOIN + j];
-    }
-    if (!live) return PSIM_OK;
-    // 3. the BFS of psim_get_graph_metrics over the seeded words: reach[]
-    // comes back with each level's words, its growth times d is the hop sum
-    TRY(lv.alloc_on(2 * ((size_t)cap + 1), st)); TRY(reach.alloc_on(PSIM_GRAPH_SOURCES, st));
-    HIP_TRY(hipMemsetAsync(next.p, 0, (size_t)N * 8, st));
-    unsigned long long prev[PSIM_FAIL_CASES] = {0}, cur[PSIM_FAIL_CASES] = {0};
-    for (uint32_t d = 1; d <= cap; d++) {
-        unsigned long long w[2] = {0, 0};
-        k_gm_push<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, N, front.p, seen.p, next.p);
-        k_gm_level<<<grid_for(N), BLK, 0, st>>>(N, next.p, seen.p, front.p, lv.p + 2 * (size_t)d, reach.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(w, lv.p + 2 * (size_t)d, sizeof w, hipMemcpyDeviceToHost, st));
-#ifndef PSIM_RS_NO_REACH_COPY                    // (timing only, `make evariant`: what this copy costs a level)
-        HIP_TRY(hipMemcpyAsync(cur, reach.p, sizeof cur, hipMemcpyDeviceToHost, st));
-#endif
-        HIP_TRY(hipStreamSynchronize(st));
-        out->levels = d;
-        if (!w[0]) break;
-        for (uint32_t j = 0; j < PSIM_FAIL_CASES; j++) {
-            if (!((w[0] >> j) & 1)) continue;
-            out->hop_sum[j] += (uint64_t)d * (cur[j] - prev[j]);
-            out->reached[j] = prev[j] = cur[j];
-            out->ecc[j] = d;
-        }
-        out->ecc_max = d;
-        if (d == cap) out->truncated = 1;
-    }
-    return PSIM_OK;
-}
-
-// a single-source BFS from the live node `root` over the rows k_tm_bfs reads,
-// a kernel per level, the level's count read back after each (zero ends it),
-// at most `cap` levels.  depth: N words; lv: cap + 1 zeroed words; per[d]: the
-// nodes first found at level d; levels, truncated: as psim_graph_metrics' are
-static int tm_bfs(hipStream_t st, const uint32_t* off, const uint8_t* cnt, const uint32_t* adj, uint32_t N,
-                  uint32_t root, uint32_t cap, uint32_t* depth, unsigned long long* lv,
-                  std::vector<uint64_t>& per, uint64_t& levels, bool& truncated) {
-    HIP_TRY(hipMemsetAsync(depth, 0xFF, (size_t)N * 4, st));
-    HIP_TRY(hipMemsetAsync(depth + root, 0, 4, st));
-    per.assign(1, 0);
-    levels = 0;
-    for (uint32_t d = 1; d <= cap; d++) {
-        unsigned long long w = 0;
-        k_tm_bfs<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, N, d, depth, lv + d);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&w, lv + d, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        levels = d;
-        if (!w) break;
-        per.push_back(w);
-        if (d == cap) truncated = true;
-    }
-    return PSIM_OK;
-}
-
-// PSIM_TREE_LANES=64: a wave a node in k_tm_rows, for A/B (DESIGN.md
-// "Broadcast tree"); anything else: the 16-lane row
-static uint32_t tm_lanes() {
-    const char* e = getenv("PSIM_TREE_LANES");
-    return e && atoi(e) == 64 ? 64u : 16u;
-}
-
-int psim_get_tree_metrics(psim_handle* h, uint32_t root, uint32_t max_levels, psim_tree_metrics* out) {
-    if (!h || !out) return PSIM_EINVAL;
-    if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE || h->hosted || !h->cfg.plumtree)
-        return PSIM_EUNSUPPORTED;                // (hosted: a collective)
-    if (h->round_open) return PSIM_ESTATE;
-    if (root >= h->N) return PSIM_ERANGE;
-    if (hipSetDevice(h->device) != hipSuccess) return PSIM_EDEVICE;
-    memset(out, 0, sizeof *out);
-    for (Shard* s : h->shards) HIP_TRY(hipStreamSynchronize(s->stream));
-    Shard* s0 = h->shards[0];
-    hipStream_t st = s0->stream;
-    const uint8_t* fl = s0->flags.p;             // replicated: every shard holds all N
-    const uint32_t N = h->N, lanes = tm_lanes();
-    // 1. T as a CSR, the same on every rank, and the entry-level counts
-    ShCsr csr;
-    TmpBuf<unsigned long long> tm, tf, sym;
-    TmpBuf<uint32_t> indeg;
-    TRY(tm.alloc_on(TM_N, st)); TRY(tf.alloc_on(TF_N, st)); TRY(sym.alloc_on(1, st)); TRY(indeg.alloc_on(N, st));
-    TRY(csr_alloc(h, st, csr));
-    auto rows = [&](const uint32_t* off, uint32_t* adj) {
-        for (Shard* s : h->shards) {
-            if (!s->n) continue;
-            const uint32_t grid = (uint32_t)(((uint64_t)s->n * lanes + BLK - 1) / BLK);
-            if (lanes == 64)
-                k_tm_rows<64><<<grid, BLK, 0, st>>>(s->hdr.p, s->act.p, s->pt_rt.p, s->pt_eag.p, s->pt_laz.p,
-                                                    s->pt_com.p, fl, s->lo, s->n, N, root, csr.cnt.p, off, adj,
-                                                    indeg.p, tm.p);
-            else
-                k_tm_rows<16><<<grid, BLK, 0, st>>>(s->hdr.p, s->act.p, s->pt_rt.p, s->pt_eag.p, s->pt_laz.p,
-                                                    s->pt_com.p, fl, s->lo, s->n, N, root, csr.cnt.p, off, adj,
-                                                    indeg.p, tm.p);
-        }
-    };
-    rows(nullptr, nullptr);
-    HIP_TRY(hipGetLastError());
-    uint32_t slot = 0;
-    TRY(csr_place(h, st, csr, slot));
-    rows(csr.off.p, csr.adj.p);
-    HIP_TRY(hipGetLastError());
-    TRY(csr_gather(h, st, csr, slot));
-    if (h->ranked) {
-        TRY(h->comm->all_reduce(tm.p, TM_N, CType::U64, COp::SUM, st));
-        TRY(h->comm->all_reduce(indeg.p, N, CType::U32, COp::SUM, st));
-    }
-    const uint32_t* off = csr.off.p;
-    const uint32_t* adj = csr.adj.p;
-    const uint8_t* cnt = csr.cnt.p;
-    k_tm_sym<<<grid_for(N), BLK, 0, st>>>(off, cnt, adj, N, sym.p);
-    HIP_TRY(hipGetLastError());
-    unsigned long long tv[TM_N], sv = 0;
-    uint8_t rf = 0;
-    HIP_TRY(hipMemcpyAsync(tv, tm.p, sizeof tv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&sv, sym.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&rf, fl + root, 1, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int k = 0; k < PSIM_HIST_BINS; k++) {
-        out->eager_out[k] = tv[TM_EOUT * PSIM_HIST_BINS + k];
-        out->lazy_out[k] = tv[TM_LOUT * PSIM_HIST_BINS + k];
-    }
-    out->n_up = tv[TM_NUP]; out->slot_nodes = tv[TM_SLOT];
-    out->eager_entries = tv[TM_EENT]; out->lazy_entries = tv[TM_LENT];
-    out->eager_links = tv[TM_ELINKS]; out->lazy_links = tv[TM_LLINKS]; out->both_links = tv[TM_BOTH];
-    out->eager_both_forms = tv[TM_FORMS]; out->self_entries = tv[TM_SELF];
-    out->eager_dead = tv[TM_EDEAD]; out->lazy_dead = tv[TM_LDEAD];
-    out->eager_nonmember = tv[TM_ENM]; out->lazy_nonmember = tv[TM_LNM];
-    out->eager_symmetric = sv;
-    out->root_live = (rf & F_UP) ? 1 : 0;
-    // 2. the two BFS passes from a live root: over T, then over the overlay's
-    // L (HyParView's gathered rows filtered as psim_get_graph_metrics does)
-    TmpBuf<uint32_t> dt, dl, gact, fadj;
-    TmpBuf<uint8_t> gan, fcnt;
-    TmpBuf<unsigned long long> lv;
-    if (out->root_live) {
-        const uint32_t cap = !max_levels || max_levels > PSIM_GRAPH_MAX_LEVELS ? PSIM_GRAPH_MAX_LEVELS : max_levels;
-        std::vector<uint64_t> per;
-        uint64_t levels = 0;
-        bool trunc = false;
-        TRY(dt.alloc_on(N, st)); TRY(dl.alloc_on(N, st)); TRY(lv.alloc_on(2 * ((size_t)cap + 1), st));
-        TRY(tm_bfs(st, off, cnt, adj, N, root, cap, dt.p, lv.p, per, levels, trunc));
-        out->levels = levels;
-        for (uint32_t d = 1; d < per.size(); d++) {
-            out->depth[d < PSIM_HIST_BINS ? d : PSIM_HIST_BINS - 1] += per[d];
-            out->depth_sum += (uint64_t)d * per[d];
-            out->reached += per[d];
-            out->depth_max = d;
-        }
-        TRY(gather_active_rows(h, st, gact, gan));
-        TRY(fadj.alloc_on((size_t)N * PSIM_ACTIVE_CAP, st)); TRY(fcnt.alloc_on(N, st));
-        k_gm_filter<<<grid_for(N), BLK, 0, st>>>(gan.p, gact.p, fl, N, fadj.p, fcnt.p);
-        TRY(tm_bfs(st, nullptr, fcnt.p, fadj.p, N, root, cap, dl.p, lv.p + cap + 1, per, levels, trunc));
-        out->truncated = trunc ? 1 : 0;
-        out->unreached = out->n_up - 1 - out->reached;
-    }
-    // 3. per node: the in-degree histogram, the two depths side by side
-    k_tm_final<<<grid_for(N), BLK, 0, st>>>(indeg.p, cnt, fl, N, root, dt.p, dl.p, tf.p);
-    HIP_TRY(hipGetLastError());
-    unsigned long long fv[TF_N];
-    HIP_TRY(hipMemcpyAsync(fv, tf.p, sizeof fv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int k = 0; k < PSIM_HIST_BINS; k++) out->eager_in[k] = fv[k];
-    out->links_from_reached = fv[TF_LFR]; out->overlay_reached = fv[TF_OREACH]; out->both_reached = fv[TF_BOTH];
-    out->depth_sum_both = fv[TF_DSUM]; out->dist_sum_both = fv[TF_LSUM];
-    out->deeper = fv[TF_DEEPER]; out->shallower = fv[TF_SHALLOWER];
-    return PSIM_OK;
-}
-
 
 // ----------------------------------------------------------- snapshot --
 // Layout: SnapHead, then per local shard a ShardHead and its arrays in

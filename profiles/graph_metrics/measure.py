@@ -40,7 +40,8 @@ def measure(n, seed, kind, reps):
         _, cluster_s = _timed(lambda: sim.graph_metrics([]), reps)
     links = h["links" if kind == "scamp" else "active_links"]
     assert g["links"] == links
-    return {"kind": kind, "nodes": n, "seed": seed, "n_up": g["n_up"], "links": links, "levels": g["levels"],
+    return {"kind": kind, "nodes": n, "seed": seed, "lib": os.environ.get("PSIM_LIB", ""), "n_up": g["n_up"],
+            "links": links, "levels": g["levels"],
             "stats_s": stats_s, "graph_s": graph_s, "clustering_only_s": cluster_s,
             "path_mean": g["dist_sum"] / max(1, g["pairs_reached"]), "path_max": g["ecc_max"],
             "pairs_unreached": g["pairs_unreached"], "sources_live": g["sources_live"],

@@ -56,7 +56,8 @@ def measure(n, seed, broadcasts, reps, host):
         for k in range(1, broadcasts + 1):
             print(f"round {int(sim.round)}: broadcast {k}", file=sys.stderr, flush=True)
             done.append(complete_broadcast(sim, 0, k))
-        out = {"nodes": n, "seed": seed, "round": int(sim.round), "broadcast_rounds": [r for r, _ in done],
+        out = {"nodes": n, "seed": seed, "lib": os.environ.get("PSIM_LIB", ""), "round": int(sim.round),
+               "broadcast_rounds": [r for r, _ in done],
                "delivered": [int(d) for _, d in done]}
         for lanes in (16, 64):
             os.environ["PSIM_TREE_LANES"] = str(lanes)
