@@ -56,7 +56,7 @@ static void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t 
 #define TWO58 ((uint64_t)1 << 58)
 
 typedef struct node {
-    uint32_t up, epoch, start_round, join_contact;
+    uint32_t epoch, start_round, join_contact;   /* (whether it runs: psim_handle.up) */
     uint64_t rng;
     uint32_t act[PSIM_ACTIVE_CAP]; uint32_t act_n;
     uint32_t pas[PSIM_PASSIVE_CAP]; uint32_t pas_n;
@@ -102,13 +102,20 @@ typedef struct msgvec { omsg *v; size_t n, cap; } msgvec;
 struct psim_handle {
     psim_config cfg;
     uint32_t N;
-    uint32_t lo, hi;                /* owned id range (sharded protocol) */
+    uint32_t lo, hi;                /* owned id range (sharded protocol, orc_create_range) */
+    /* The rows of the owned ids only (hi - lo of them: nodes, sn, origin, and
+     * in_beg with one more), reached by global id through nd / snd / ibeg /
+     * orig below.  What every party knows of every id -- whether it runs, its
+     * partition group, the crash and omission marks, the view-order table --
+     * is one byte per id of the whole space. */
     node *nodes;
+    uint8_t *up;                    /* N: the node's manager runs */
     uint8_t *part, *crashed_now;
+    int crashed_any;                /* crashed_now holds a mark of this round */
     uint64_t round;
     msgvec inbox, out;              /* inbox sorted by (dst, src, seq) */
     int oom;                        /* a round buffer could not grow: steps fail from then on */
-    size_t *in_beg;                 /* N+1 offsets into inbox */
+    size_t *in_beg;                 /* hi - lo + 1 offsets into inbox */
     /* pending events */
     uint32_t *pend_crash; size_t pend_crash_n, pend_crash_cap;
     uint32_t *pend_join, *pend_contact; size_t pend_join_n, pend_join_cap;
@@ -119,7 +126,7 @@ struct psim_handle {
     uint32_t pend_b_root[PSIM_MSG_SLOTS], pend_b_msg[PSIM_MSG_SLOTS]; uint32_t pend_b_n;
     /* message slots: the id owning slot k and its root (node_spec map identity) */
     uint32_t slot_msg[PSIM_MSG_SLOTS], slot_root[PSIM_MSG_SLOTS];
-    uint32_t *origin;               /* per node: message id + 1 it originates this round, 0 = none */
+    uint32_t *origin;               /* per owned node: message id + 1 it originates this round, 0 = none */
     uint32_t tracked_msg;
     psim_round_stats *st;           /* stats of the round being executed */
     /* PLUGGABLE handles */
@@ -138,6 +145,13 @@ struct psim_handle {
     uint8_t *btab;                  /* low 8 bits of erlang:phash(NodeSpec, 2^32) - 1 per node
                                        (orc_set_phash_table / orc_set_bucket_table), NULL = stand-in */
 };
+
+/* the rows of an owned id */
+static int owned(const struct psim_handle *h, uint32_t id) { return id >= h->lo && id < h->hi; }
+static node *nd(const struct psim_handle *h, uint32_t id) { return &h->nodes[id - h->lo]; }
+static snode *snd(const struct psim_handle *h, uint32_t id) { return &h->sn[id - h->lo]; }
+static size_t *ibeg(const struct psim_handle *h, uint32_t id) { return &h->in_beg[id - h->lo]; }
+static uint32_t *orig(const struct psim_handle *h, uint32_t id) { return &h->origin[id - h->lo]; }
 
 /* per-node execution context */
 typedef struct ctx {
@@ -398,7 +412,7 @@ static void emit(ctx *c, uint32_t dst, uint32_t type, uint32_t ttl, uint32_t a0,
 static int connect_ok(ctx *c, uint32_t dst) {
     struct psim_handle *h = c->h;
     if (dst >= h->N || dst == c->me) return 0;
-    return h->nodes[dst].up && h->part[dst] == h->part[c->me];
+    return h->up[dst] && h->part[dst] == h->part[c->me];
 }
 
 /* ------------------------------------------------------ connections -- */
@@ -634,7 +648,7 @@ uint32_t orc_xbot_latency(uint64_t seed, uint32_t a, uint32_t b) {
 
 /* net_adm:ping/1 answers pong: the node runs (pings go over distributed
  * Erlang, not partisan: a partition does not stop them) */
-static int xb_pong(ctx *c, uint32_t p) { return p == c->me || (p < c->h->N && c->h->nodes[p].up); }
+static int xb_pong(ctx *c, uint32_t p) { return p == c->me || (p < c->h->N && c->h->up[p]); }
 
 /* is_better(latency, New, Old) at the deciding node (xbot:1318-1333) */
 static int xb_better(ctx *c, uint32_t nw, uint32_t old) {
@@ -889,7 +903,7 @@ static void pt_update(ctx *c, uint32_t from, uint32_t root, int to_eager) {
  * group. */
 static int pt_conn(ctx *c, uint32_t ident) {
     uint32_t id = ident & ~PSIM_MAP_BIT;
-    return !(id == c->me || id >= c->h->N || !conn_has(c, id) || !c->h->nodes[id].up ||
+    return !(id == c->me || id >= c->h->N || !conn_has(c, id) || !c->h->up[id] ||
              c->h->part[id] != c->h->part[c->me]);
 }
 
@@ -1144,10 +1158,10 @@ static int timer_due(uint32_t period, uint64_t r, uint32_t start) {
 }
 
 static void process_node(struct psim_handle *h, uint32_t n) {
-    node *s = &h->nodes[n];
+    node *s = nd(h, n);
     ctx c = {h, s, n, 0, PSIM_NONE, 0, 0, 0, 0};
     uint64_t r = h->round;
-    size_t b = h->in_beg[n], e = h->in_beg[n + 1];
+    size_t b = ibeg(h, n)[0], e = ibeg(h, n)[1];
     /* a fresh incarnation has no connections: traffic addressed to the
      * previous one is lost */
     if (s->start_round == r && e > b) { h->st->dropped += e - b; e = b; }
@@ -1155,7 +1169,7 @@ static void process_node(struct psim_handle *h, uint32_t n) {
     /* a due promotion timer is work only if it can act (hv:547-551) */
     int promo_work = promo && s->act_n < h->cfg.min_active_size;
     int shuf = timer_due(h->cfg.shuffle_period, r, s->start_round);
-    int origin = h->origin[n] != 0 && h->cfg.plumtree;
+    int origin = *orig(h, n) != 0 && h->cfg.plumtree;
     int lazy_due = h->cfg.plumtree && timer_due(h->cfg.lazy_tick_period, r, s->start_round);
     int lazy = lazy_due && s->out_n > 0;
     int xbot = is_xbot(h) && timer_due(h->cfg.xbot_period, r, s->start_round);
@@ -1237,7 +1251,7 @@ static void process_node(struct psim_handle *h, uint32_t n) {
         }
 
     if (origin) {                                  /* plumtree:282-287, backend:179-200 */
-        uint32_t my = n | PSIM_MAP_BIT, msg = h->origin[n] - 1;
+        uint32_t my = n | PSIM_MAP_BIT, msg = *orig(h, n) - 1;
         s->have |= 1ull << (msg % PSIM_MSG_SLOTS);
         if (msg == h->tracked_msg) { s->trk_round = (uint32_t)r; s->trk_hop = 0; }
         pt_push(&c, msg, 0, my, my);
@@ -1273,7 +1287,7 @@ static uint32_t fb_mem(const struct psim_handle *h, const uint32_t *b, uint32_t 
 static uint32_t pl_member(ctx *c, uint32_t p) {
     struct psim_handle *h = c->h;
     if (h->cfg.strategy == PSIM_STRATEGY_FULL) return (fb_mem(h, fb_row(h, c->me), p >> 5) >> (p & 31u)) & 1u;
-    snode *q = &h->sn[c->me];
+    snode *q = snd(h, c->me);
     return (uint32_t)list_member(q->view, q->view_n, p);
 }
 
@@ -1315,7 +1329,7 @@ static int pl_send(ctx *c, uint32_t dst, uint32_t type, uint32_t a0, uint32_t sl
     /* full: every target comes from the node's own member row, or is an old
      * member whose connection is still open (leave/1) */
     int full = c->h->cfg.strategy == PSIM_STRATEGY_FULL;
-    if (!connect_ok(c, dst) || !(full || pl_member(c, dst) || dst == c->h->sn[c->me].pending)) {
+    if (!connect_ok(c, dst) || !(full || pl_member(c, dst) || dst == snd(c->h, c->me)->pending)) {
         c->h->st->send_fail++;
         return 0;
     }
@@ -1426,7 +1440,7 @@ static uint32_t random_0_or_1(ctx *c) { return uniform_n(c, 10) >= 5 ? 1u : 0u; 
 static void scamp_add(ctx *c, uint32_t *l, uint32_t *n, uint32_t e, int as_set) {
     if (as_set && list_member(l, *n, e)) return;
     if (*n >= PSIM_SVIEW_CAP) { ovf(c, PSIM_OVF_STRATEGY); return; }
-    if (as_set) { set_add(c->h, l, n, e, &c->h->sn[c->me].view_slots); return; }
+    if (as_set) { set_add(c->h, l, n, e, &snd(c->h, c->me)->view_slots); return; }
     for (uint32_t i = *n; i > 0; i--) l[i] = l[i - 1];
     l[0] = e;
     (*n)++;
@@ -1437,7 +1451,7 @@ static void scamp_add(ctx *c, uint32_t *l, uint32_t *n, uint32_t e, int as_set) 
  * to every member known before (v1: sets:fold/3, the reverse of to_list;
  * v2: lists:foldl/3) and to C (v1) / C - 1 (v2) random ones of them. */
 static void scamp_join(ctx *c, uint32_t contact) {
-    snode *q = &c->h->sn[c->me];
+    snode *q = snd(c->h, c->me);
     int v1 = c->h->cfg.strategy == PSIM_STRATEGY_SCAMP_V1;
     uint32_t m0[PSIM_SVIEW_CAP], n0 = q->view_n;
     memcpy(m0, q->view, sizeof m0);
@@ -1457,7 +1471,7 @@ static void scamp_join(ctx *c, uint32_t contact) {
  * rounds of 1 s, any earlier round) -> forward_subscription(Myself) to one
  * random member; then a ping to every member. */
 static void scamp_periodic(ctx *c) {
-    snode *q = &c->h->sn[c->me];
+    snode *q = snd(c->h, c->me);
     uint32_t m[PSIM_SVIEW_CAP], n = q->view_n;
     memcpy(m, q->view, sizeof m);
     int isolated = q->last_ping != PSIM_NONE && (uint32_t)c->h->round > q->last_ping;
@@ -1472,7 +1486,7 @@ static void scamp_periodic(ctx *c) {
  * subscription is kept iff the draw is 0 and Node is not a member yet (v2
  * then asks Node to keep us); otherwise it is forwarded to one random member */
 static void scamp_fwd(ctx *c, uint32_t node) {
-    snode *q = &c->h->sn[c->me];
+    snode *q = snd(c->h, c->me);
     int v1 = c->h->cfg.strategy == PSIM_STRATEGY_SCAMP_V1;
     uint32_t rnd = random_0_or_1(c);
     if (rnd == 0 && !list_member(q->view, q->view_n, node)) {
@@ -1493,7 +1507,7 @@ static void scamp_fwd(ctx *c, uint32_t node) {
  *   v2 leave/2 (scamp_v2:116-127): {bootstrap_remove_subscription, t} to every
  *      member of the partial view, no state change. */
 static void scamp_leave(ctx *c, uint32_t t) {
-    snode *q = &c->h->sn[c->me];
+    snode *q = snd(c->h, c->me);
     uint32_t m0[PSIM_SVIEW_CAP], n0 = q->view_n;
     memcpy(m0, q->view, sizeof m0);
     int v1 = c->h->cfg.strategy == PSIM_STRATEGY_SCAMP_V1;
@@ -1526,7 +1540,7 @@ static void full_leave(ctx *c, uint32_t t) {
 /* ------------------------------------------------------------- driver -- */
 static void pl_handle(ctx *c, const omsg *m) {
     struct psim_handle *h = c->h;
-    snode *q = &h->sn[c->me];
+    snode *q = snd(h, c->me);
     int full = h->cfg.strategy == PSIM_STRATEGY_FULL;
     switch (m->type) {
     case PSIM_PL_HELLO:       /* the server's answer: {state, Tag, get_local_state()} */
@@ -1584,11 +1598,11 @@ static void pl_handle(ctx *c, const omsg *m) {
 int orc_crash(struct psim_handle *h, const uint32_t *nodes, size_t n);
 
 static void pl_process_node(struct psim_handle *h, uint32_t n) {
-    node *s = &h->nodes[n];
-    snode *q = &h->sn[n];
+    node *s = nd(h, n);
+    snode *q = snd(h, n);
     ctx c = {h, s, n, 0, PSIM_NONE, 0, 0, 0, 0};
     uint64_t r = h->round;
-    size_t b = h->in_beg[n], e = h->in_beg[n + 1];
+    size_t b = ibeg(h, n)[0], e = ibeg(h, n)[1];
     if (s->start_round == r && e > b) { h->st->dropped += e - b; e = b; }
     int hello = q->pending != PSIM_NONE && !q->hello_sent;
     int periodic = timer_due(h->cfg.periodic_interval, r, s->start_round);
@@ -1638,7 +1652,7 @@ static void pl_process_node(struct psim_handle *h, uint32_t n) {
 }
 
 static void pl_node_init(struct psim_handle *h, uint32_t n, uint32_t contact) {
-    snode *q = &h->sn[n];
+    snode *q = snd(h, n);
     memset(q, 0, sizeof *q);
     q->started = 1;
     q->pending = contact;
@@ -1655,10 +1669,11 @@ static void pl_node_init(struct psim_handle *h, uint32_t n, uint32_t contact) {
 
 /* ---------------------------------------------------------- rounds -- */
 static void node_init(struct psim_handle *h, uint32_t n, uint32_t contact) {
-    node *s = &h->nodes[n];
+    h->up[n] = 1;
+    if (!owned(h, n)) return;                    /* another party's node: here it only runs */
+    node *s = nd(h, n);
     uint32_t ep = h->cfg.persist_epoch ? s->epoch + 1 : 1;
     memset(s, 0, sizeof *s);
-    s->up = 1;
     s->epoch = ep;
     s->start_round = (uint32_t)h->round;
     s->join_contact = contact;
@@ -1686,13 +1701,13 @@ static void round_begin(struct psim_handle *h, psim_round_stats *st) {
     h->st = st;
     for (size_t i = 0; i < h->pend_crash_n; i++) {
         uint32_t n = h->pend_crash[i];
-        if (h->nodes[n].up) { h->nodes[n].up = 0; h->crashed_now[n] = 1; }
+        if (h->up[n]) { h->up[n] = 0; h->crashed_now[n] = 1; h->crashed_any = 1; }
     }
     for (size_t i = 0; i < h->pend_join_n; i++) {
         node_init(h, h->pend_join[i], h->pend_contact[i]);
         h->pend_join_mark[h->pend_join[i]] = 0;
     }
-    for (size_t i = 0; i < h->pend_lv_n; i++) h->sn[h->pend_lv_a[i]].leave_tgt = h->pend_lv_t[i] + 1;
+    for (size_t i = 0; i < h->pend_lv_n; i++) snd(h, h->pend_lv_a[i])->leave_tgt = h->pend_lv_t[i] + 1;
     h->pend_lv_n = 0;
     if (h->pend_part_clear) memset(h->part, 0, h->N);
     if (h->pend_part_set) memcpy(h->part, h->pend_part, h->N);
@@ -1708,7 +1723,7 @@ static void round_begin(struct psim_handle *h, psim_round_stats *st) {
     /* broadcasts: each takes its message slot (the slot's previous id is
      * retired: its delivery bit cleared everywhere) and is originated this
      * round at its root if the root runs; the last one is the tracked one */
-    for (uint32_t n = 0; n < h->N; n++) h->origin[n] = 0;
+    memset(h->origin, 0, (size_t)(h->hi - h->lo) * sizeof(uint32_t));
     if (h->pend_b_n) {
         uint64_t clear = 0;
         for (uint32_t i = 0; i < h->pend_b_n; i++) {
@@ -1716,13 +1731,14 @@ static void round_begin(struct psim_handle *h, psim_round_stats *st) {
             clear |= 1ull << k;
             h->slot_msg[k] = h->pend_b_msg[i];
             h->slot_root[k] = h->pend_b_root[i] | PSIM_MAP_BIT;
-            if (h->nodes[h->pend_b_root[i]].up) h->origin[h->pend_b_root[i]] = h->pend_b_msg[i] + 1;
+            uint32_t root = h->pend_b_root[i];
+            if (owned(h, root) && h->up[root]) *orig(h, root) = h->pend_b_msg[i] + 1;
         }
         h->tracked_msg = h->pend_b_msg[h->pend_b_n - 1];
-        for (uint32_t n = 0; n < h->N; n++) {
-            h->nodes[n].have &= ~clear;
-            h->nodes[n].trk_round = PSIM_NONE;
-            h->nodes[n].trk_hop = 0;
+        for (uint32_t n = h->lo; n < h->hi; n++) {
+            nd(h, n)->have &= ~clear;
+            nd(h, n)->trk_round = PSIM_NONE;
+            nd(h, n)->trk_hop = 0;
         }
     }
     h->pend_crash_n = h->pend_join_n = 0;
@@ -1731,15 +1747,15 @@ static void round_begin(struct psim_handle *h, psim_round_stats *st) {
 
     h->out.n = 0;
     for (uint32_t n = h->lo; n < h->hi; n++) {
-        if (h->nodes[n].up) {
+        if (h->up[n]) {
             st->nodes_up++;
             if (is_pl(h)) pl_process_node(h, n);
             else process_node(h, n);
         } else {
-            st->dropped += h->in_beg[n + 1] - h->in_beg[n];
+            st->dropped += ibeg(h, n)[1] - ibeg(h, n)[0];
         }
     }
-    memset(h->crashed_now, 0, h->N);
+    if (h->crashed_any) { memset(h->crashed_now, 0, h->N); h->crashed_any = 0; }
 }
 
 /* Round, second half: the messages addressed to the owned nodes (from every
@@ -1755,9 +1771,9 @@ static void round_end(struct psim_handle *h, msgvec *in) {
         msgvec t = h->inbox; h->inbox = *in; *in = t;
     }
     size_t j = 0;
-    for (uint32_t n = 0; n <= h->N; n++) {
+    for (uint32_t n = h->lo; n <= h->hi; n++) {
         while (j < h->inbox.n && h->inbox.v[j].dst < n) j++;
-        h->in_beg[n] = j;
+        *ibeg(h, n) = j;
     }
     h->round++;
 }
@@ -1783,7 +1799,14 @@ void orc_default_config(psim_config *cfg) {
     cfg->xbot_period = 35;
 }
 
-int orc_create(const psim_config *cfg, struct psim_handle **out) {
+/* A handle that owns the ids [lo, hi) of cfg->n_nodes: rows for those ids
+ * only, one byte per id of the whole space for what every party knows of
+ * every node.  Every event call is made on it, for the other ids too; an id
+ * nobody ever started never runs (connect_ok fails, nothing is sent to it).
+ * A round is orc_round_emit / orc_get_outbox / orc_round_absorb (below); the
+ * getters answer for owned ids, in global numbering.  cfg's shard_world and
+ * shard_rank are not read. */
+static int range_create(const psim_config *cfg, uint32_t lo, uint32_t hi, struct psim_handle **out) {
     if (!cfg || !out || cfg->abi_version != PSIM_ABI_VERSION || cfg->n_nodes == 0 ||
         cfg->n_nodes >= PSIM_MAP_BIT || cfg->max_active_size < 2 ||
         cfg->max_active_size > PSIM_ACTIVE_CAP || cfg->max_passive_size < 1 ||
@@ -1793,26 +1816,23 @@ int orc_create(const psim_config *cfg, struct psim_handle **out) {
         cfg->fanout > 64 || cfg->strict > 1)
         return PSIM_EINVAL;
     int full = cfg->manager == PSIM_MANAGER_PLUGGABLE && cfg->strategy == PSIM_STRATEGY_FULL;
-    if (full && cfg->shard_world > 1) return PSIM_EUNSUPPORTED;   /* payloads are shard-local */
+    if (full && (lo != 0 || hi != cfg->n_nodes)) return PSIM_EUNSUPPORTED;   /* payloads are shard-local */
+    if (lo > hi || hi > cfg->n_nodes) return PSIM_EINVAL;
     struct psim_handle *h = (struct psim_handle *)calloc(1, sizeof *h);
     if (!h) return PSIM_ENOMEM;
     h->cfg = *cfg;
     h->N = cfg->n_nodes;
-    h->lo = 0; h->hi = h->N;
-    if (cfg->shard_world > 1) {
-        if (cfg->shard_rank >= cfg->shard_world || cfg->shard_world > h->N) { free(h); return PSIM_EINVAL; }
-        uint32_t per = (h->N + cfg->shard_world - 1) / cfg->shard_world;
-        h->lo = cfg->shard_rank * per < h->N ? cfg->shard_rank * per : h->N;
-        h->hi = h->lo + per < h->N ? h->lo + per : h->N;
-    }
-    h->nodes = (node *)calloc(h->N, sizeof(node));
+    h->lo = lo; h->hi = hi;
+    size_t rows = (size_t)(hi - lo) + 1;             /* (a rank past the last id owns none) */
+    h->nodes = (node *)calloc(rows, sizeof(node));
+    h->up = (uint8_t *)calloc(h->N, 1);
     h->part = (uint8_t *)calloc(h->N, 1);
     h->crashed_now = (uint8_t *)calloc(h->N, 1);
-    h->in_beg = (size_t *)calloc((size_t)h->N + 1, sizeof(size_t));
+    h->in_beg = (size_t *)calloc(rows, sizeof(size_t));
     h->pend_part = (uint8_t *)calloc(h->N, 1);
-    if (!h->nodes || !h->part || !h->crashed_now || !h->in_beg || !h->pend_part) return PSIM_ENOMEM;
+    if (!h->nodes || !h->up || !h->part || !h->crashed_now || !h->in_beg || !h->pend_part) return PSIM_ENOMEM;
     if (cfg->manager == PSIM_MANAGER_PLUGGABLE) {
-        h->sn = (snode *)calloc(h->N, sizeof(snode));
+        h->sn = (snode *)calloc(rows, sizeof(snode));
         if (!h->sn) return PSIM_ENOMEM;
         if (full) {
             h->W = (h->N + 31) / 32;
@@ -1820,7 +1840,7 @@ int orc_create(const psim_config *cfg, struct psim_handle **out) {
             if (!h->fbits) return PSIM_ENOMEM;
         }
     }
-    h->origin = (uint32_t *)calloc(h->N, sizeof(uint32_t));
+    h->origin = (uint32_t *)calloc(rows, sizeof(uint32_t));
     h->flt.faulted = (uint8_t *)calloc(h->N, 1);
     h->nx.faulted = (uint8_t *)calloc(h->N, 1);
     if (!h->origin || !h->flt.faulted || !h->nx.faulted) return PSIM_ENOMEM;
@@ -1830,9 +1850,29 @@ int orc_create(const psim_config *cfg, struct psim_handle **out) {
     return PSIM_OK;
 }
 
+int orc_create_range(const psim_config *cfg, uint32_t lo, uint32_t hi, struct psim_handle **out) {
+    if (lo >= hi) return PSIM_EINVAL;
+    return range_create(cfg, lo, hi, out);
+}
+
+/* every id, or with cfg->shard_world > 1 the rank's cut: per = ceil(n / world)
+ * ids a rank (a cut that is no cut is the range 1..0 no handle has) */
+int orc_create(const psim_config *cfg, struct psim_handle **out) {
+    uint32_t lo = 0, hi = cfg ? cfg->n_nodes : 0;
+    if (cfg && cfg->shard_world > 1) {
+        lo = 1; hi = 0;
+        if (cfg->shard_rank < cfg->shard_world && cfg->shard_world <= cfg->n_nodes) {
+            uint32_t per = (cfg->n_nodes + cfg->shard_world - 1) / cfg->shard_world;
+            lo = cfg->shard_rank * per < cfg->n_nodes ? cfg->shard_rank * per : cfg->n_nodes;
+            hi = lo + per < cfg->n_nodes ? lo + per : cfg->n_nodes;
+        }
+    }
+    return range_create(cfg, lo, hi, out);
+}
+
 void orc_destroy(struct psim_handle *h) {
     if (!h) return;
-    free(h->nodes); free(h->part); free(h->crashed_now); free(h->in_beg); free(h->pend_part);
+    free(h->nodes); free(h->up); free(h->part); free(h->crashed_now); free(h->in_beg); free(h->pend_part);
     free(h->inbox.v); free(h->out.v);
     free(h->pend_crash); free(h->pend_join); free(h->pend_contact); free(h->pend_join_mark); free(h->origin);
     free(h->pend_lv_a); free(h->pend_lv_t);
@@ -1856,11 +1896,11 @@ int orc_join(struct psim_handle *h, const uint32_t *nodes, const uint32_t *conta
     }
     if (h->fbits) {                 /* an ORSet re-add would need per-incarnation tokens */
         for (size_t i = 0; i < n; i++)
-            if (h->sn[nodes[i]].started) {
+            if (snd(h, nodes[i])->started) {
                 for (size_t j = 0; j < n; j++) h->pend_join_mark[nodes[j]] = 0;
                 return PSIM_EUNSUPPORTED;
             }
-        for (size_t i = 0; i < n; i++) h->sn[nodes[i]].started = 1;
+        for (size_t i = 0; i < n; i++) snd(h, nodes[i])->started = 1;
     }
     if (h->pend_join_n + n > h->pend_join_cap) {
         h->pend_join_cap = (h->pend_join_n + n) * 2;
@@ -2015,12 +2055,12 @@ int orc_step(struct psim_handle *h, uint32_t n_rounds, psim_round_stats *stats) 
 int orc_get_round(struct psim_handle *h, uint64_t *round) { *round = h->round; return PSIM_OK; }
 
 int orc_get_nodes(struct psim_handle *h, uint32_t first, uint32_t count, psim_node_view *out) {
-    if ((uint64_t)first + count > h->N) return PSIM_ERANGE;
+    if (first < h->lo || (uint64_t)first + count > h->hi) return PSIM_ERANGE;
     for (uint32_t k = 0; k < count; k++) {
-        const node *s = &h->nodes[first + k];
+        const node *s = nd(h, first + k);
         psim_node_view *v = &out[k];
         memset(v, 0, sizeof *v);
-        v->up = s->up; v->epoch = s->epoch; v->start_round = s->start_round;
+        v->up = h->up[first + k]; v->epoch = s->epoch; v->start_round = s->start_round;
         v->rng_ctr = s->rng;
         v->act_n = s->act_n; v->pas_n = s->pas_n;
         memcpy(v->act, s->act, sizeof v->act); memcpy(v->pas, s->pas, sizeof v->pas);
@@ -2057,10 +2097,10 @@ int orc_get_msg_slots(struct psim_handle *h, uint32_t *ids, uint32_t *roots, siz
 /* Delivery of the tracked broadcast (psim_get_delivery). */
 int orc_get_delivery(struct psim_handle *h, uint32_t first, uint32_t count, uint8_t *have, uint32_t *round,
                      uint32_t *hop) {
-    if ((uint64_t)first + count > h->N) return PSIM_ERANGE;
+    if (first < h->lo || (uint64_t)first + count > h->hi) return PSIM_ERANGE;
     uint64_t bit = h->tracked_msg == PSIM_NONE ? 0ull : 1ull << (h->tracked_msg % PSIM_MSG_SLOTS);
     for (uint32_t k = 0; k < count; k++) {
-        const node *s = &h->nodes[first + k];
+        const node *s = nd(h, first + k);
         have[k] = (s->have & bit) ? 1 : 0;
         round[k] = s->trk_round;
         hop[k] = s->trk_hop;
@@ -2078,7 +2118,7 @@ static uint32_t uf_find(uint32_t *p, uint32_t x) {
  * in-degrees counted link by link, symmetry by scanning the peer's view,
  * components by union-find over live active links. */
 int orc_get_histograms(struct psim_handle *h, psim_histograms *out) {
-    if (is_pl(h)) return PSIM_EUNSUPPORTED;
+    if (is_pl(h) || h->lo != 0 || h->hi != h->N) return PSIM_EUNSUPPORTED;   /* (it reads every row) */
     memset(out, 0, sizeof *out);
     uint32_t N = h->N;
     uint32_t *ina = calloc(N, 4), *inp = calloc(N, 4), *par = malloc((size_t)N * 4), *sz = calloc(N, 4);
@@ -2086,18 +2126,18 @@ int orc_get_histograms(struct psim_handle *h, psim_histograms *out) {
     uint64_t bit = h->tracked_msg == PSIM_NONE ? 0ull : 1ull << (h->tracked_msg % PSIM_MSG_SLOTS);
     for (uint32_t i = 0; i < N; i++) par[i] = i;
     for (uint32_t i = 0; i < N; i++) {
-        const node *s = &h->nodes[i];
-        if (!s->up) continue;
+        const node *s = nd(h, i);
+        if (!h->up[i]) continue;
         out->n_up++;
         uint32_t deg = 0;
         for (uint32_t k = 0; k < s->act_n; k++) {
             uint32_t p = s->act[k];
             if (p == i) continue;
             deg++;
-            if (!h->nodes[p].up) continue;
+            if (!h->up[p]) continue;
             ina[p]++;
             out->active_links++;
-            const node *q = &h->nodes[p];
+            const node *q = nd(h, p);
             for (uint32_t j = 0; j < q->act_n; j++)
                 if (q->act[j] == i) { out->symmetric_links++; break; }
             uint32_t a = uf_find(par, i), b = uf_find(par, p);
@@ -2105,7 +2145,7 @@ int orc_get_histograms(struct psim_handle *h, psim_histograms *out) {
         }
         for (uint32_t k = 0; k < s->pas_n; k++) {
             uint32_t p = s->pas[k];
-            if (p != i && h->nodes[p].up) inp[p]++;
+            if (p != i && h->up[p]) inp[p]++;
         }
         out->active_out[hbin(deg)]++;
         out->passive_fill[hbin(s->pas_n)]++;
@@ -2116,7 +2156,7 @@ int orc_get_histograms(struct psim_handle *h, psim_histograms *out) {
         }
     }
     for (uint32_t i = 0; i < N; i++) {
-        if (!h->nodes[i].up) continue;
+        if (!h->up[i]) continue;
         out->active_in[hbin(ina[i])]++;
         out->passive_in[hbin(inp[i])]++;
         uint32_t r = uf_find(par, i);
@@ -2136,14 +2176,14 @@ static uint64_t members_hash(struct psim_handle *h, const uint32_t *b) {
 
 int orc_get_strategy_nodes(struct psim_handle *h, uint32_t first, uint32_t count, psim_strategy_view *out) {
     if (!is_pl(h)) return PSIM_ESTATE;
-    if ((uint64_t)first + count > h->N) return PSIM_ERANGE;
+    if (first < h->lo || (uint64_t)first + count > h->hi) return PSIM_ERANGE;
     for (uint32_t k = 0; k < count; k++) {
         uint32_t n = first + k;
-        const node *s = &h->nodes[n];
-        const snode *q = &h->sn[n];
+        const node *s = nd(h, n);
+        const snode *q = snd(h, n);
         psim_strategy_view *v = &out[k];
         memset(v, 0, sizeof *v);
-        v->up = s->up; v->start_round = s->start_round; v->rng_ctr = s->rng;
+        v->up = h->up[n]; v->start_round = s->start_round; v->rng_ctr = s->rng;
         v->pending = q->started ? q->pending : PSIM_NONE;
         v->last_ping = q->started ? q->last_ping : PSIM_NONE;
         v->view_n = q->view_n; v->in_n = q->inv_n;

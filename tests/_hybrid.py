@@ -9,6 +9,12 @@ engine=False plays the engine's ranks with oracle shards too: the expected
 side of the exchange check, and the check that the protocol itself equals
 the unsharded oracle.
 
+Hybrid(cfg, parties=[(lo, hi, ENGINE | ORACLE), ...]) takes explicit ranges
+instead (tests/_high_ids.py: id windows far from 0): an oracle party is an
+orc_create_range handle, ids in no party's range are never started, and a
+record addressed to one fails the run.  One party alone is the one-party
+driver: nothing may leave it, so its outbound list is empty every round.
+
 Every party gets every event call.  A round: every party emits; the records
 are dealt by destination; every party's import is shuffled by a seeded
 permutation; every party absorbs; the stats are summed, `round` from one.
@@ -43,25 +49,17 @@ def _first_diff(a, b):
     return f"record {k}: {a[k].tolist()} against {b[k].tolist()}"
 
 
-class OracleShard(Oracle):
-    """One rank of the oracle's sharded protocol (orc_round_emit /
-    orc_get_outbox / orc_round_absorb)."""
-
-    def __init__(self, cfg, world, rank):
-        c = type(cfg).from_buffer_copy(cfg)
-        c.comm_id = None
-        c.shard_world, c.shard_rank = world, rank
-        super().__init__(c)
-        per = (cfg.n_nodes + world - 1) // world
-        self.lo, self.hi = min(cfg.n_nodes, rank * per), min(cfg.n_nodes, (rank + 1) * per)
-        self._st = None
+class _Rounds:
+    """a round in its two halves (orc_round_emit / orc_get_outbox /
+    orc_round_absorb)"""
+    _st = None
 
     def emit(self):
         self._st = np.zeros(1, _abi.STATS_DTYPE)
         assert self._lib.orc_round_emit(self._h, self._st.ctypes.data) == 0
 
     def outbound(self):
-        """every record the rank emitted, its own range's included"""
+        """every record the party emitted, its own range's included"""
         n = C.c_size_t()
         self._lib.orc_get_outbox(self._h, None, 0, C.byref(n))
         box = np.zeros((n.value, 16), np.uint32)
@@ -74,26 +72,72 @@ class OracleShard(Oracle):
         return self._st
 
 
+class OracleShard(_Rounds, Oracle):
+    """One rank of the oracle's sharded protocol: orc_create's equal cut."""
+
+    def __init__(self, cfg, world, rank):
+        c = type(cfg).from_buffer_copy(cfg)
+        c.comm_id = None
+        c.shard_world, c.shard_rank = world, rank
+        super().__init__(c)
+        per = (cfg.n_nodes + world - 1) // world
+        self.lo, self.hi = min(cfg.n_nodes, rank * per), min(cfg.n_nodes, (rank + 1) * per)
+
+
+class OracleRange(_Rounds, Oracle):
+    """An oracle that owns the ids [lo, hi) of cfg.n_nodes (orc_create_range)."""
+
+    def __init__(self, cfg, lo, hi):
+        c = type(cfg).from_buffer_copy(cfg)
+        c.comm_id = None
+        c.shard_world, c.shard_rank = 1, 0
+        super().__init__(c, lo, hi)
+
+
+ENGINE, ORACLE = "engine", "oracle"
+
+
 class Hybrid:
-    def __init__(self, cfg, world, ranks, engine=True, seed=2024, expect=None, resume_at=None, probes=None,
-                 on_outbound=None):
+    """Hybrid(cfg, world, ranks): the equal cut of the module's head.
+    Hybrid(cfg, parties=[(lo, hi, ENGINE | ORACLE), ...]): explicit ranges in
+    id order, at most one of them the engine's (engine=False: an OracleRange
+    plays it, and the trace is still that range's).  Ids in no party's range
+    are never started: a record addressed to one fails the run."""
+
+    def __init__(self, cfg, world=None, ranks=None, engine=True, seed=2024, expect=None, resume_at=None, probes=None,
+                 on_outbound=None, parties=None, on_records=None):
         from partisan_amd.sim import HostSim
 
         n = cfg.n_nodes
         self.cfg, self.n, self.world = cfg, n, world
-        self.per = (n + world - 1) // world
-        r0, r1 = ranks
-        self.lo, self.hi = r0 * self.per, min(n, r1 * self.per)
         self._seed = seed
         self.engine = None
         self.parties = []                    # in id order: each has .lo and .hi
-        for r in range(world):
-            if r0 <= r < r1 and engine:
-                if r == r0:
-                    self.engine = HostSim(type(cfg).from_buffer_copy(cfg), self.lo, self.hi)
+        if parties is None:
+            self.per = (n + world - 1) // world
+            r0, r1 = ranks
+            self.lo, self.hi = r0 * self.per, min(n, r1 * self.per)
+            self.first, self.end = 0, n
+            for r in range(world):
+                if r0 <= r < r1 and engine:
+                    if r == r0:
+                        self.engine = HostSim(type(cfg).from_buffer_copy(cfg), self.lo, self.hi)
+                        self.parties.append(self.engine)
+                else:
+                    self.parties.append(OracleShard(cfg, world, r))
+        else:
+            assert all(a[0] < a[1] <= b[0] for a, b in zip(parties, parties[1:])) and parties[-1][0] < parties[-1][1] <= n
+            mine = [p for p in parties if p[2] == ENGINE]
+            assert len(mine) <= 1
+            # (no engine range: the first party's is the one the trace follows)
+            self.lo, self.hi = (mine or parties)[0][:2]
+            self.first, self.end = parties[0][0], parties[-1][1]
+            for lo, hi, kind in parties:
+                if kind == ENGINE and engine:
+                    self.engine = HostSim(type(cfg).from_buffer_copy(cfg), lo, hi)
                     self.parties.append(self.engine)
-            else:
-                self.parties.append(OracleShard(cfg, world, r))
+                else:
+                    self.parties.append(OracleRange(cfg, lo, hi))
         # the exchange of every round, as this run saw it: the records that
         # left [lo, hi) -- those for ids below first, then those for ids at or
         # above, each side in (src, seq) order -- and the ones that entered it
@@ -103,6 +147,7 @@ class Hybrid:
         self.n_out = self.n_in = 0
         self.resumed = False
         self.tables = []
+        self.on_records = on_records         # on_records(round, every record of the round)
 
     # ---- events: every party makes the same call
     def _all(self, name, *a):
@@ -146,7 +191,8 @@ class Hybrid:
 
     # ---- inspection: each party answers for the ids it owns
     def _owned(self, name, first, count):
-        count = self.n - first if count is None else count
+        first = self.first if first is None else first
+        count = self.end - first if count is None else count
         parts = []
         for p in self.parties:
             lo, hi = max(first, p.lo), min(first + count, p.hi)
@@ -154,13 +200,13 @@ class Hybrid:
                 parts.append(getattr(p, name)(lo, hi - lo))
         return parts
 
-    def nodes(self, first=0, count=None):
+    def nodes(self, first=None, count=None):
         return np.concatenate(self._owned("nodes", first, count))
 
-    def strategy_nodes(self, first=0, count=None):
+    def strategy_nodes(self, first=None, count=None):
         return np.concatenate(self._owned("strategy_nodes", first, count))
 
-    def delivery(self, first=0, count=None):
+    def delivery(self, first=None, count=None):
         p = self._owned("delivery", first, count)
         return tuple(np.concatenate([x[i] for x in p]) for i in range(3))
 
@@ -195,6 +241,12 @@ class Hybrid:
             boxes.append(box)
         # what crossed the engine range's boundary, from the senders' side
         every = np.concatenate(boxes)
+        held = np.zeros(len(every), bool)
+        for p in self.parties:
+            held |= (every[:, 0] >= p.lo) & (every[:, 0] < p.hi)
+        assert held.all(), f"round {r}: a record for an id no party owns: {every[~held][0].tolist()}"
+        if self.on_records is not None:
+            self.on_records(r, every)
         src_in, dst_in = self._inside(every[:, 1]), self._inside(every[:, 0])
         out = every[src_in & ~dst_in]
         out = np.concatenate([canonical(out[out[:, 0] < self.lo]), canonical(out[out[:, 0] >= self.hi])])

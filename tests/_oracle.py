@@ -43,9 +43,20 @@ def load():
 
 
 class Oracle(_Driver):
-    def __init__(self, cfg):
+    """Oracle(cfg): every id of cfg.n_nodes.  Oracle(cfg, lo, hi): a range
+    handle (orc_create_range) with rows for the ids [lo, hi) only; its rounds
+    are orc_round_emit / orc_get_outbox / orc_round_absorb (tests/_hybrid.py)
+    and its getters answer for owned ids, in global numbering."""
+
+    def __init__(self, cfg, lo=None, hi=None):
         lib = load()
-        super().__init__(_abi.bind(lib, "orc_", _abi.SIGNATURES), cfg)
+        api = _abi.bind(lib, "orc_", _abi.SIGNATURES)
+        if lo is not None:
+            lib.orc_create_range.restype = C.c_int
+            lib.orc_create_range.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+            api["create"] = lambda cfg_ref, h_ref: lib.orc_create_range(cfg_ref, lo, hi, h_ref)
+            self.lo, self.hi = lo, hi
+        super().__init__(api, cfg)
         self._lib = lib
 
     def inbox(self):

@@ -16,6 +16,7 @@ An entry returns what its scenario returns: (handle, stats, ...)."""
 import numpy as np
 
 import _config_cases as CC
+import _high_ids as HI
 import _random_schedule as R
 import _scenarios as S
 from _hybrid import Hybrid
@@ -159,8 +160,8 @@ _rare("full_leave_absent_f0_w3", _p(S.full_leave_absent, n=72, started=24),
       [_WAS, _WAS_W + "0: was | F", _WAS_W + "1: w == (t >> 5) | F"], kind="pl")
 _rare("full_leave_absent_f5", _p(S.full_leave_absent, n=72, started=64, fanout=5), [_WAS], kind="pl")
 _rare("pending_keep", _p(S.pending_keep),
-      ["pl_send | if (!connect_ok(c, dst) || !(full || pl_member(c, dst) || dst == c->h->sn[c->me].pending)) { | "
-       "3: dst == c->h->sn[c->me].pending | T"], kind="pl")
+      ["pl_send | if (!connect_ok(c, dst) || !(full || pl_member(c, dst) || dst == snd(c->h, c->me)->pending)) { | "
+       "3: dst == snd(c->h, c->me)->pending | T"], kind="pl")
 
 
 def runs():
@@ -189,6 +190,26 @@ def runs():
                 out[f"random-hybrid:{kind}-{seed}"] = (lambda kind, seed: lambda make: R.execute(
                     R.hybrid_make(engine=False), R.generate(kind, seed, host=True), R.path("oracle-sharded")[1]))(
                         kind, seed)
+    # tests/test_gpu_high_ids.py: the range oracle (orc_create_range) the engine
+    # is compared with in the id windows, as one party and as two that
+    # exchange; `make` is not used
+    for k in HI.SCENARIOS:
+        for w in ("top", "2^26", "2^24"):
+            out[f"high-ids:{k}@{w}"] = (lambda k, w: lambda make: HI.run(k, HI.at_ids(
+                HI.one_party(), *reversed(HI.windows(HI.size_of(k))[w])), **HI.gpu_kw(k, w)))(k, w)
+    for k in HI.BOUNDARY:
+        out[f"high-ids-split:{k}"] = (lambda k: lambda make: HI.run(k, HI.at_ids(
+            HI.split(("engine", "oracle"), engine=False), *reversed(HI.windows(HI.size_of(k))["top"])),
+            **HI.gpu_kw(k, "top")))(k)
+    out["high-ids:buckets@2^24"] = lambda make: HI.run("churn_partition", S.with_buckets(HI.at_ids(
+        HI.one_party(), *reversed(HI.windows(1024)["2^24"])), 12))
+    for kind in R.KINDS:
+        if kind != "full":
+            for seed in R.CORPUS_SEEDS[kind][:2]:
+                out[f"high-ids-random:{kind}-{seed}"] = (lambda kind, seed: lambda make: R.execute(
+                    HI.at_ids(HI.one_party(), HI.TOP - R.generate(kind, seed, host=True).n, HI.TOP),
+                    R.generate(kind, seed, host=True, rounds=HI.RANDOM_TOP_ROUNDS),
+                    R.path("oracle-sharded")[1]))(kind, seed)
     for k in SETS_V1:
         out["sets_v1:" + k] = sets_v1(k)
     for k, f in RARE.items():

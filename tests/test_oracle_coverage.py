@@ -70,9 +70,13 @@ def test_rare_scenario_takes_its_outcome(coverage, name):
 
 def test_rare_targets_are_taken_by_no_older_run(coverage):
     """each target was never taken before its scenario existed: no run outside
-    tests/test_gpu_rare_branches.py takes it"""
+    tests/test_gpu_rare_branches.py takes it -- of the runs that are older
+    than the scenarios.  The id-window runs (tests/test_gpu_high_ids.py,
+    `high-ids...`) came later and are other overlays: one of them takes the
+    GRAFT for a message the receiver does not hold."""
     per_run, _ = coverage
-    others = T.total({k: v for k, v in per_run.items() if not k.startswith("rare:")})
+    assert any(k.startswith("high-ids") for k in per_run)
+    others = T.total({k: v for k, v in per_run.items() if not k.startswith(("rare:", "high-ids"))})
     for name, keys in P.RARE_TARGETS.items():
         for key in keys:
             assert others.get(key, 0) == 0, (name, key)
