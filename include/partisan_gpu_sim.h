@@ -503,6 +503,61 @@ typedef struct psim_resilience {
     uint64_t reserved[8];
 } psim_resilience;
 
+/* Gossip with a fanout over the overlay, under the failure cases of
+ * psim_resilience, computed on the device (DESIGN.md "Gossip with a fanout"):
+ * the other side of that experiment -- a node pushes to at most `fanout` of
+ * its links instead of flooding all of them.  Up to PSIM_FAIL_CASES cases in
+ * one bit-parallel BFS; everything is an integer, so the struct is bit-exact
+ * whatever the order of any sum.
+ *   mix64, u, L, the live cases and A_j are psim_resilience's: for the same
+ *     (source, threshold, salt, fail_seed) alive[j] is the same number.  N(i):
+ *     the targets of i's links in L, k_i = |N(i)| (psim_graph_metrics).  View
+ *     entries that name down nodes are not in L, so they are no candidates.
+ *   h(i, salt) = mix64(fail_seed ^ mix64(((uint64_t)salt << 32) | i)), so
+ *     u(v, salt) = (uint32_t)(h(v, salt) >> 32).
+ *   w(i, p, salt) = mix64(h(i, salt) + 0x9E3779B97F4A7C15 * (p + 1)) (64-bit,
+ *     wrapping).  S_j(i), the targets node i pushes to in case j: N(i) if
+ *     fanout_j == 0 or fanout_j >= k_i; otherwise the fanout_j ids p of N(i)
+ *     with the smallest (w(i, p, salt_j), p).  The choice depends on the set
+ *     N(i), not on the order of a view, so it is the same for any shard count.
+ *   A node chooses among all of N(i), the nodes failed in the case included:
+ *     the failure is not yet detected (before any healing), and a copy to such
+ *     a target is lost.
+ *   Infect-and-die: a node sends once, when first reached, to S_j(i).  G_j:
+ *     the pairs (i, p) with i, p in A_j and p in S_j(i).  The BFS from
+ *     source_j over G_j runs levels d = 1, 2, ... while d <= the level cap; a
+ *     level that finds no node in any case ends it.
+ *   The senders of case j: the source and every node reached at a distance
+ *     below the level cap.
+ *   Liveness is the only other filter: partitions are ignored, as in every
+ *     statistics call.  A dead source's case is skipped and its slots stay
+ *     zero. */
+typedef struct psim_gossip_case {
+    uint32_t source;     /* the gossip starts here; it never fails in its own case */
+    uint32_t threshold;  /* node v != source fails iff u(v, salt) < threshold (as psim_failure_case) */
+    uint32_t salt;       /* failure set and target choice; equal salts: nested failure sets, same choices */
+    uint32_t fanout;     /* 0: every link (a flood); f > 0: at most f links per node */
+} psim_gossip_case;
+typedef struct psim_gossip_reach {
+    uint64_t n_up;                           /* live nodes */
+    uint64_t links;                          /* |L| */
+    uint64_t cases_live;                     /* number of live cases */
+    uint64_t live_mask;                      /* bit j set: case j is live */
+    uint64_t alive[PSIM_FAIL_CASES];         /* |A_j| */
+    uint64_t reached[PSIM_FAIL_CASES];       /* nodes v != source_j at finite directed distance from
+                                                source_j over G_j; reliability = reached / (alive - 1) */
+    uint64_t hop_sum[PSIM_FAIL_CASES];       /* the exact sum of those distances */
+    uint64_t ecc[PSIM_FAIL_CASES];           /* the largest finite distance */
+    uint64_t sent[PSIM_FAIL_CASES];          /* copies sent: the sum of |S_j(i)| over the senders */
+    uint64_t lost[PSIM_FAIL_CASES];          /* ... of which to a target outside A_j; sent - lost -
+                                                reached: the copies that arrive at a node that has one */
+    uint64_t ecc_max;                        /* the largest ecc[j] */
+    uint64_t levels;                         /* BFS levels run (the last one may have found nothing) */
+    uint64_t truncated;                      /* 1: the level cap ended the BFS with level `cap` still
+                                                finding a node; those nodes do not send */
+    uint64_t reserved[8];
+} psim_gossip_reach;
+
 typedef struct psim_handle psim_handle;
 
 void psim_default_config(psim_config *cfg);
@@ -684,6 +739,21 @@ int psim_get_tree_metrics(psim_handle *h, uint32_t root, uint32_t max_levels, ps
  * same struct).  No Erlang binding yet. */
 int psim_get_resilience(psim_handle *h, const psim_failure_case *cases, size_t n_cases, uint64_t fail_seed,
                         uint32_t max_levels, psim_resilience *out);
+/* Reach and cost of a gossip with a fanout under up to PSIM_FAIL_CASES cases
+ * (psim_gossip_reach above), on the device, for HyParView, X-BOT and SCAMP
+ * v1 / v2 handles of any shard count; slot j of every per-case array is
+ * cases[j].  Any fanout is legal, and two cases may name the same source.
+ * n_cases == 0 fills n_up and links only.  max_levels caps the BFS: 0 means
+ * PSIM_GRAPH_MAX_LEVELS, and larger values are clamped to it.  Errors, in this
+ * order: PSIM_EINVAL for a null h or out, null cases with n_cases > 0 or
+ * n_cases > PSIM_FAIL_CASES; PSIM_EUNSUPPORTED for full-membership and
+ * host-exchange handles; PSIM_ESTATE with a round open; PSIM_ERANGE for a
+ * source >= n_nodes (a dead source is legal and skipped).  Read-only: the
+ * rounds stepped after it are those of a run without it.  A collective on
+ * rank handles (every rank calls with the same arguments; every rank gets the
+ * same struct).  No Erlang binding yet. */
+int psim_get_gossip_reach(psim_handle *h, const psim_gossip_case *cases, size_t n_cases, uint64_t fail_seed,
+                          uint32_t max_levels, psim_gossip_reach *out);
 /* Snapshot of the whole simulation state of this process (node rows,
  * in-flight messages, round, events not yet applied are not included):
  * with buf == NULL (or cap too small) only *need is set.  psim_restore

@@ -194,6 +194,21 @@ class PsimResilience(C.Structure):
     ]
 
 
+class PsimGossipCase(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("threshold", C.c_uint32), ("salt", C.c_uint32), ("fanout", C.c_uint32)]
+
+
+class PsimGossipReach(C.Structure):
+    _fields_ = [
+        ("n_up", C.c_uint64), ("links", C.c_uint64), ("cases_live", C.c_uint64), ("live_mask", C.c_uint64),
+        ("alive", C.c_uint64 * FAIL_CASES), ("reached", C.c_uint64 * FAIL_CASES),
+        ("hop_sum", C.c_uint64 * FAIL_CASES), ("ecc", C.c_uint64 * FAIL_CASES),
+        ("sent", C.c_uint64 * FAIL_CASES), ("lost", C.c_uint64 * FAIL_CASES),
+        ("ecc_max", C.c_uint64), ("levels", C.c_uint64), ("truncated", C.c_uint64),
+        ("reserved", C.c_uint64 * 8),
+    ]
+
+
 NODE_VIEW_DTYPE = np.dtype(PsimNodeView)
 STRATEGY_VIEW_DTYPE = np.dtype(PsimStrategyView)
 STATS_DTYPE = np.dtype(PsimRoundStats)
@@ -247,6 +262,8 @@ GPU_ONLY = {
     "get_tree_metrics": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(PsimTreeMetrics)]),
     "get_resilience": (C.c_int, [_H, C.POINTER(PsimFailureCase), C.c_size_t, C.c_uint64, C.c_uint32,
                                  C.POINTER(PsimResilience)]),
+    "get_gossip_reach": (C.c_int, [_H, C.POINTER(PsimGossipCase), C.c_size_t, C.c_uint64, C.c_uint32,
+                                   C.POINTER(PsimGossipReach)]),
     # the message trace (no oracle twin: the tests filter Oracle.inbox())
     "trace_watch": (C.c_int, [_H, _P32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_size_t]),
     "trace_read": (C.c_int, [_H, _P32, _P32, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),

@@ -1,9 +1,10 @@
-// psim_metrics.hip -- the read-only analyses of the overlay behind five
+// psim_metrics.hip -- the read-only analyses of the overlay behind six
 // getters of include/partisan_gpu_sim.h; no round runs any of it:
 //   psim_get_histograms           HyParView's views, the tracked broadcast, components
 //   psim_get_strategy_histograms  the pluggable strategies' views (SCAMP's as a CSR)
 //   psim_get_graph_metrics        clustering, and a BFS from 64 sources at once
 //   psim_get_resilience           that BFS over 64 mass-failure cases
+//   psim_get_gossip_reach         ... pushed over at most `fanout` links a node
 //   psim_get_tree_metrics         a Plumtree root's eager tree against the overlay
 // Each waits for every shard's stream, works on the first shard's, and is a
 // collective on ranks.  Shared by the analyses: Links (a link set as rows) and
@@ -30,7 +31,8 @@ struct Links {
     const uint32_t* off;
     const uint8_t* cnt;
     const uint32_t* adj;
-    DEV const uint32_t* row(uint32_t i) const { return adj + (off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP); }
+    DEV size_t slot(uint32_t i) const { return off ? (size_t)off[i] : (size_t)i * PSIM_ACTIVE_CAP; }   // of i's first link
+    DEV const uint32_t* row(uint32_t i) const { return adj + slot(i); }
     DEV const uint32_t* csr_row(uint32_t i) const { return adj + off[i]; }   // (a kernel of one form only: no test)
     DEV const uint32_t* hv_row(uint32_t i) const { return adj + (size_t)i * PSIM_ACTIVE_CAP; }
 };
@@ -55,6 +57,23 @@ DEV void tile_add(unsigned long long* tile, uint64_t w, uint64_t todo) {
     }
 }
 DEV void tile_add(unsigned long long* tile, uint64_t w) { tile_add(tile, w, wave_or(w)); }
+// A lane's count of up to 255 words per bit, as 8 counter planes: plane b
+// holds bit b of the count of every bit j.  plane_inc counts the word m;
+// tile_add_planes adds the wave's counts of every bit j of todo into the tile
+DEV void plane_inc(unsigned long long (&pl)[8], unsigned long long m) {
+#pragma unroll
+    for (int b = 0; b < 8; b++) { const unsigned long long t = pl[b] & m; pl[b] ^= m; m = t; }
+}
+DEV void tile_add_planes(unsigned long long* tile, const unsigned long long (&pl)[8], uint64_t todo) {
+    while (todo) {                                    // (uniform)
+        const int j = ffs64(todo);
+        todo &= todo - 1;
+        uint32_t s = 0;
+#pragma unroll
+        for (int b = 0; b < 8; b++) s += popc(ballot((pl[b] >> j) & 1)) << b;
+        if (lane_id() == 0) atomicAdd(&tile[j], (unsigned long long)s);
+    }
+}
 
 // --------------------------------------------------------- overlay stats --
 // psim_get_histograms: per live node its view sizes, the in-degree links it
@@ -692,24 +711,14 @@ __global__ void __launch_bounds__(BLK) k_rs_census(Links ln, const uint8_t* __re
             if (!m) continue;
             ho |= m;
             if (m & ~inw[p]) atomicOr(&inw[p], m);
-            unsigned long long carry = m;
-#pragma unroll
-            for (int b = 0; b < 8; b++) { const unsigned long long t = pl[b] & carry; pl[b] ^= carry; carry = t; }
+            plane_inc(pl, m);
         }
     }
     const uint32_t lsum = sh_wave_sum(c);
     if (lsum && lane_id() == 0) atomicAdd(&sh_l, (unsigned long long)lsum);
     if (ballot(a != 0)) {                             // (uniform)
         tile_add(sh_noout, a & ~ho);
-        uint64_t todo = wave_or(ho);
-        while (todo) {
-            const int j = ffs64(todo);
-            todo &= todo - 1;
-            uint32_t s = 0;
-#pragma unroll
-            for (int b = 0; b < 8; b++) s += popc(ballot((pl[b] >> j) & 1)) << b;
-            if (lane_id() == 0) atomicAdd(&sh_links[j], (unsigned long long)s);
-        }
+        tile_add_planes(sh_links, pl, wave_or(ho));
     }
     __syncthreads();
     if (threadIdx.x < PSIM_FAIL_CASES) {
@@ -736,6 +745,202 @@ __global__ void __launch_bounds__(BLK) k_rs_sweep(uint32_t n, const unsigned lon
         if (sh_alive[threadIdx.x]) atomicAdd(&rs[RS_ALIVE + threadIdx.x], sh_alive[threadIdx.x]);
         if (sh_noin[threadIdx.x]) atomicAdd(&rs[RS_NOIN + threadIdx.x], sh_noin[threadIdx.x]);
     }
+}
+
+// ------------------------------------------------- gossip with a fanout --
+// psim_get_gossip_reach (psim_gossip_reach in the header defines every field):
+// k_rs_alive's survivor words and the k_gm_level BFS, with one more word per
+// link slot: bit j of sel[e] = "link e = (i, p) is in S_j(i)", e the slot of
+// the link in Links.adj.
+//   k_go_select      rows of at most GO_SHORT links: a thread a node, the
+//                    row's ids, keys and ranks in registers
+//   k_go_select_long the longer rows of a CSR: GO_LN lanes a node, entry
+//                    c * GO_LN + g in slot c of the group's lane g; an entry's
+//                    rank = the entries of the row before it in (w, id) order,
+//                    counted by broadcasting every entry across the group
+//                    both walk the case table in k_rs_alive's order: h, the
+//                    keys and the ranks once per distinct salt, a case is one
+//                    compare of the rank against its fanout; a row no longer
+//                    than the smallest fanout above 0 (fmin) is chosen whole
+//                    in every case and pays none of it
+//   k_go_push        k_gm_push over the chosen links: m = front[i] & sel[e]
+//   k_go_tally       after the loop: the senders word of i is seen[i] &
+//                    alive[i] & ~front[i] (front: only a truncated last level);
+//                    over i's links m = that word & sel[e] counted per bit into
+//                    sent, m & ~alive[p] into lost; alive[] per bit; |L|
+// The case table `par`: k_rs_alive's, then GO_FAN, the fanouts in its order.
+enum { GO_FAN = RS_PAR, GO_PAR = RS_PAR + 64 };
+enum { GO_ALIVE = 0, GO_SENT = 64, GO_LOST = 128, GO_L = 192, GO_N = 193 };
+constexpr uint64_t GO_GOLDEN = 0x9E3779B97F4A7C15ull;
+// Row lengths (DESIGN.md "Gossip with a fanout"): every HyParView row and
+// 99.3 % of SCAMP v2's (c = 5, 2^24 nodes: 69 % hold one link, the longest 54)
+// have at most 8 links -- a thread; of the rest most have at most 16, and a
+// v1 row can pass 100 -- 16 lanes, up to 8 entries each
+constexpr uint32_t GO_SHORT = 8, GO_LN = 16, GO_C = PSIM_SVIEW_CAP / GO_LN;
+
+// entry (ka, pa) comes before entry (kb, pb) in the order S_j(i) is cut from
+DEV bool go_before(uint64_t ka, uint32_t pa, uint64_t kb, uint32_t pb) { return ka < kb || (ka == kb && pa < pb); }
+DEV uint64_t go_h(uint64_t fail_seed, uint32_t salt, uint32_t i) { return mix64(fail_seed ^ mix64(((uint64_t)salt << 32) | i)); }
+DEV uint64_t go_key(uint64_t h, uint32_t p) { return mix64(h + GO_GOLDEN * ((uint64_t)p + 1)); }
+
+// all: the bits of every case; fmin: the smallest fanout above 0 (none: PSIM_NONE)
+__global__ void __launch_bounds__(BLK) k_go_select(Links ln, uint32_t n, const uint32_t* __restrict__ par,
+                                                   uint32_t nc, uint64_t fail_seed, unsigned long long all,
+                                                   uint32_t fmin, unsigned long long* sel) {
+    static_assert(PSIM_ACTIVE_CAP <= GO_SHORT, "every HyParView row is a short one");
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t c = i < n ? ln.cnt[i] : 0;
+    if (!c || c > GO_SHORT) return;                   // (the longer rows: k_go_select_long's)
+    const size_t at = ln.slot(i);
+    if (c <= fmin) {
+        for (uint32_t r = 0; r < c; r++) sel[at + r] = all;
+        return;
+    }
+    // (entries past c: the last of every order, and never stored)
+    uint32_t p[GO_SHORT], rank[GO_SHORT];
+    uint64_t key[GO_SHORT];
+    unsigned long long w[GO_SHORT];
+#pragma unroll
+    for (uint32_t r = 0; r < GO_SHORT; r++) { p[r] = r < c ? ln.adj[at + r] : PSIM_NONE; rank[r] = 0; key[r] = 0; w[r] = 0; }
+    for (uint32_t q = 0; q < nc; q++) {               // (uniform)
+        const uint32_t salt = par[RS_SALT + q];
+        if (!q || salt != par[RS_SALT + q - 1]) {
+            const uint64_t h = go_h(fail_seed, salt, i);
+#pragma unroll
+            for (uint32_t r = 0; r < GO_SHORT; r++) key[r] = r < c ? go_key(h, p[r]) : ~0ull;
+#pragma unroll
+            for (uint32_t r = 0; r < GO_SHORT; r++) rank[r] = 0;
+            // (a pair once: one of two entries comes first, a row's ids are distinct)
+#pragma unroll
+            for (uint32_t r = 0; r < GO_SHORT; r++)
+#pragma unroll
+                for (uint32_t t = r + 1; t < GO_SHORT; t++) {
+                    const uint32_t tf = go_before(key[t], p[t], key[r], p[r]) ? 1u : 0u;
+                    rank[r] += tf; rank[t] += 1u - tf;
+                }
+        }
+        const uint32_t f = par[GO_FAN + q];
+        const unsigned long long bit = 1ull << par[RS_SLOT + q];
+#pragma unroll
+        for (uint32_t r = 0; r < GO_SHORT; r++)
+            if (!f || rank[r] < f) w[r] |= bit;
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < GO_SHORT; r++)
+        if (r < c) sel[at + r] = w[r];
+}
+
+// (the loop bounds are the same in all lanes of a group, and a lane reads its
+// own group only, as in tm_match)
+__global__ void __launch_bounds__(BLK) k_go_select_long(Links ln, uint32_t n, const uint32_t* __restrict__ par,
+                                                        uint32_t nc, uint64_t fail_seed, unsigned long long all,
+                                                        uint32_t fmin, unsigned long long* sel) {
+    static_assert(GO_LN * GO_C == PSIM_SVIEW_CAP && 64 % GO_LN == 0, "a group holds a whole row and sits in one wave");
+    const uint32_t i = (uint32_t)(((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / GO_LN);
+    const uint32_t l = lane_id(), g = l % GO_LN, gb = l - g;
+    const uint32_t c = i < n ? min((uint32_t)ln.cnt[i], (uint32_t)PSIM_SVIEW_CAP) : 0;
+    if (c <= GO_SHORT) return;                        // (k_go_select's)
+    const uint32_t nch = (c + GO_LN - 1) / GO_LN;     // slots in use
+    const size_t at = ln.off[i];
+    if (c <= fmin) {
+        for (uint32_t e = g; e < c; e += GO_LN) sel[at + e] = all;
+        return;
+    }
+    uint32_t p[GO_C], rank[GO_C];
+    uint64_t key[GO_C];
+    unsigned long long w[GO_C];
+#pragma unroll
+    for (uint32_t s = 0; s < GO_C; s++) { p[s] = s * GO_LN + g < c ? ln.adj[at + s * GO_LN + g] : PSIM_NONE; rank[s] = 0; key[s] = 0; w[s] = 0; }
+    for (uint32_t q = 0; q < nc; q++) {               // (uniform)
+        const uint32_t salt = par[RS_SALT + q];
+        if (!q || salt != par[RS_SALT + q - 1]) {
+            const uint64_t h = go_h(fail_seed, salt, i);
+#pragma unroll
+            for (uint32_t s = 0; s < GO_C; s++) {
+                if (s < nch) key[s] = s * GO_LN + g < c ? go_key(h, p[s]) : ~0ull;
+                rank[s] = 0;
+            }
+#pragma unroll
+            for (uint32_t s2 = 0; s2 < GO_C; s2++)
+                for (uint32_t y = 0; y < GO_LN && s2 * GO_LN + y < c; y++) {
+                    const uint64_t kv = shfl64(key[s2], (int)(gb + y));
+                    const uint32_t pv = shfl(p[s2], (int)(gb + y));
+#pragma unroll
+                    for (uint32_t s = 0; s < GO_C; s++)
+                        if (s < nch) rank[s] += go_before(kv, pv, key[s], p[s]) ? 1u : 0u;
+                }
+        }
+        const uint32_t f = par[GO_FAN + q];
+        const unsigned long long bit = 1ull << par[RS_SLOT + q];
+#pragma unroll
+        for (uint32_t s = 0; s < GO_C; s++)
+            if (!f || rank[s] < f) w[s] |= bit;
+    }
+#pragma unroll
+    for (uint32_t s = 0; s < GO_C; s++)
+        if (s * GO_LN + g < c) sel[at + s * GO_LN + g] = w[s];
+}
+
+// a node on the frontier ORs the bits that chose a link into its target if that lacks one of them
+__global__ void k_go_push(Links ln, const unsigned long long* __restrict__ sel, uint32_t n,
+                          const unsigned long long* __restrict__ front, const unsigned long long* __restrict__ seen,
+                          unsigned long long* next) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long f = front[i];
+    if (!f) return;
+    const size_t at = ln.slot(i);
+    for (uint32_t k = 0, c = ln.cnt[i]; k < c; k++) {
+        const unsigned long long m = f & sel[at + k];
+        if (!m) continue;
+        const uint32_t p = ln.adj[at + k];
+        if (m & ~seen[p]) atomicOr(&next[p], m);
+    }
+}
+
+// (a node that is down holds no links and no alive bit)
+__global__ void __launch_bounds__(BLK) k_go_tally(Links ln, const unsigned long long* __restrict__ sel, uint32_t n,
+                                                  const unsigned long long* __restrict__ alive,
+                                                  const unsigned long long* __restrict__ seen,
+                                                  const unsigned long long* __restrict__ front,
+                                                  unsigned long long* go) {
+    static_assert(PSIM_SVIEW_CAP < 256 && PSIM_ACTIVE_CAP < 256, "a row's copies per case fit the 8 counter planes");
+    __shared__ unsigned long long sh_alive[PSIM_FAIL_CASES], sh_sent[PSIM_FAIL_CASES], sh_lost[PSIM_FAIL_CASES], sh_l;
+    if (threadIdx.x < PSIM_FAIL_CASES) { sh_alive[threadIdx.x] = 0; sh_sent[threadIdx.x] = 0; sh_lost[threadIdx.x] = 0; }
+    if (threadIdx.x == 0) sh_l = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t c = i < n ? ln.cnt[i] : 0;
+    const unsigned long long a = i < n ? alive[i] : 0;
+    const unsigned long long sw = a ? a & seen[i] & ~front[i] : 0;
+    unsigned long long ps[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pl[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hs = 0, hl = 0;
+    if (sw) {
+        const size_t at = ln.slot(i);
+        for (uint32_t k = 0; k < c; k++) {
+            const unsigned long long m = sw & sel[at + k];
+            if (!m) continue;
+            hs |= m;
+            plane_inc(ps, m);
+            const unsigned long long ml = m & ~alive[ln.adj[at + k]];
+            if (!ml) continue;
+            hl |= ml;
+            plane_inc(pl, ml);
+        }
+    }
+    const uint32_t lsum = sh_wave_sum(c);
+    if (lsum && lane_id() == 0) atomicAdd(&sh_l, (unsigned long long)lsum);
+    if (ballot(a != 0)) {                             // (uniform)
+        tile_add(sh_alive, a);
+        tile_add_planes(sh_sent, ps, wave_or(hs));
+        tile_add_planes(sh_lost, pl, wave_or(hl));
+    }
+    __syncthreads();
+    if (threadIdx.x < PSIM_FAIL_CASES) {
+        if (sh_alive[threadIdx.x]) atomicAdd(&go[GO_ALIVE + threadIdx.x], sh_alive[threadIdx.x]);
+        if (sh_sent[threadIdx.x]) atomicAdd(&go[GO_SENT + threadIdx.x], sh_sent[threadIdx.x]);
+        if (sh_lost[threadIdx.x]) atomicAdd(&go[GO_LOST + threadIdx.x], sh_lost[threadIdx.x]);
+    }
+    if (threadIdx.x == 0 && sh_l) atomicAdd(&go[GO_L], sh_l);
 }
 
 // ------------------------------------------------------ broadcast tree --
@@ -1230,6 +1435,7 @@ static int sh_build_csr(psim_handle* h, hipStream_t st, unsigned long long* sl, 
 // every reader sees the same L.  LinkSet owns the buffers behind its Links
 struct LinkSet {
     Links ln;
+    size_t slots = 0;                            // link slots behind ln.adj
     ShCsr csr;
     TmpBuf<unsigned long long> sl;               // (the count pass's statistics: not reported)
     TmpBuf<uint32_t> gact, fadj;
@@ -1240,32 +1446,36 @@ static int link_set(psim_handle* h, hipStream_t st, const uint8_t* fl, LinkSet& 
         TRY(s.sl.alloc_on(SL_N, st));
         TRY(sh_build_csr(h, st, s.sl.p, s.csr));
         s.ln = s.csr.links();
+        s.slots = s.csr.adj.n;
     } else {
         const uint32_t N = h->N;
         TRY(gather_active_rows(h, st, s.gact, s.gan));
         TRY(s.fadj.alloc_on((size_t)N * PSIM_ACTIVE_CAP, st)); TRY(s.fcnt.alloc_on(N, st));
         k_gm_filter<<<grid_for(N), BLK, 0, st>>>(s.gan.p, s.gact.p, fl, N, s.fadj.p, s.fcnt.p);
         s.ln = Links{nullptr, s.fcnt.p, s.fadj.p};
+        s.slots = (size_t)N * PSIM_ACTIVE_CAP;
     }
     return PSIM_OK;
 }
 
-// The word BFS (k_gm_push, k_gm_level): bit j of a node's word = reached in
-// slot j.  seen, front: seeded by the caller; next: zero; lv: 2 (cap + 1)
+// The word BFS (a push kernel, k_gm_level): bit j of a node's word = reached
+// in slot j.  seen, front: seeded by the caller; next: zero; lv: 2 (cap + 1)
 // zeroed words, a pair a level; reach: a count per slot
 struct WordBfs { TmpBuf<unsigned long long> seen, front, next, lv, reach; };
-// Its level loop over ln: a push and a level kernel per level, the level's
-// two words -- w[0] the OR of its new bits, w[1] their number -- read back
-// after each, and reach[] with them into `cur` where the caller wants it per
-// level (nullptr: not).  Zero new bits end it, at most `cap` levels; f(d, w)
-// for every level that found something; out: levels, ecc_max, truncated
-template <class Out, class F>
-static int bfs_levels(hipStream_t st, Links ln, uint32_t N, uint32_t cap, WordBfs& b, unsigned long long* cur,
-                      Out* out, F f) {
+// Its level loop: push() launches the kernel that ORs the frontier's words
+// into next (k_gm_push over every link, k_go_push over the chosen ones), then
+// the level kernel; the level's two words -- w[0] the OR of its new bits, w[1]
+// their number -- are read back after each, and reach[] with them into `cur`
+// where the caller wants it per level (nullptr: not).  Zero new bits end it,
+// at most `cap` levels; f(d, w) for every level that found something; out:
+// levels, ecc_max, truncated
+template <class Out, class Push, class F>
+static int bfs_levels(hipStream_t st, uint32_t N, uint32_t cap, WordBfs& b, unsigned long long* cur, Out* out,
+                      Push push, F f) {
     for (uint32_t d = 1; d <= cap; d++) {
         unsigned long long w[2] = {0, 0};
         unsigned long long* lv = b.lv.p + 2 * (size_t)d;
-        k_gm_push<<<grid_for(N), BLK, 0, st>>>(ln, N, b.front.p, b.seen.p, b.next.p);
+        push();
         k_gm_level<<<grid_for(N), BLK, 0, st>>>(N, b.next.p, b.seen.p, b.front.p, lv, b.reach.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(w, lv, sizeof w, hipMemcpyDeviceToHost, st));
@@ -1280,6 +1490,20 @@ static int bfs_levels(hipStream_t st, Links ln, uint32_t N, uint32_t cap, WordBf
         if (d == cap) out->truncated = 1;
     }
     return PSIM_OK;
+}
+
+// bfs_levels' f of a getter with a case per slot: cur is reach[] as read back
+// with level d, its growth since prev times d is the level's share of the hop sum
+template <class Out>
+static auto case_levels(Out* out, const unsigned long long* cur, unsigned long long* prev) {
+    return [=](uint32_t d, const unsigned long long* w) {
+        for (uint32_t j = 0; j < PSIM_FAIL_CASES; j++) {
+            if (!((w[0] >> j) & 1)) continue;
+            out->hop_sum[j] += (uint64_t)d * (cur[j] - prev[j]);
+            out->reached[j] = prev[j] = cur[j];
+            out->ecc[j] = d;
+        }
+    };
 }
 
 extern "C" int psim_get_strategy_histograms(psim_handle* h, psim_strategy_histograms* out) {
@@ -1374,7 +1598,8 @@ extern "C" int psim_get_graph_metrics(psim_handle* h, const uint32_t* sources, s
     TRY(read_back(st, &live, b.lv.p));
     out->sources_live = (uint64_t)__builtin_popcountll(live);
     if (!live) return PSIM_OK;
-    TRY(bfs_levels(st, ls.ln, N, cap, b, nullptr, out, [&](uint32_t d, const unsigned long long* w) {
+    const auto push = [&] { k_gm_push<<<grid_for(N), BLK, 0, st>>>(ls.ln, N, b.front.p, b.seen.p, b.next.p); };
+    TRY(bfs_levels(st, N, cap, b, nullptr, out, push, [&](uint32_t d, const unsigned long long* w) {
         out->dist[d < PSIM_HIST_BINS ? d : PSIM_HIST_BINS - 1] += w[1];
         out->dist_sum += (uint64_t)d * w[1];
         out->pairs_reached += w[1];
@@ -1444,14 +1669,80 @@ extern "C" int psim_get_resilience(psim_handle* h, const psim_failure_case* case
     TRY(b.lv.alloc_on(2 * ((size_t)cap + 1), st)); TRY(b.reach.alloc_on(PSIM_GRAPH_SOURCES, st));
     HIP_TRY(hipMemsetAsync(b.next.p, 0, (size_t)N * 8, st));
     unsigned long long prev[PSIM_FAIL_CASES] = {0}, cur[PSIM_FAIL_CASES] = {0};
-    return bfs_levels(st, ls.ln, N, cap, b, cur, out, [&](uint32_t d, const unsigned long long* w) {
-        for (uint32_t j = 0; j < PSIM_FAIL_CASES; j++) {
-            if (!((w[0] >> j) & 1)) continue;
-            out->hop_sum[j] += (uint64_t)d * (cur[j] - prev[j]);
-            out->reached[j] = prev[j] = cur[j];
-            out->ecc[j] = d;
-        }
-    });
+    const auto push = [&] { k_gm_push<<<grid_for(N), BLK, 0, st>>>(ls.ln, N, b.front.p, b.seen.p, b.next.p); };
+    return bfs_levels(st, N, cap, b, cur, out, push, case_levels(out, cur, prev));
+}
+
+extern "C" int psim_get_gossip_reach(psim_handle* h, const psim_gossip_case* cases, size_t n_cases, uint64_t fail_seed,
+                                     uint32_t max_levels, psim_gossip_reach* out) {
+    if (!h || !out || (n_cases && !cases) || n_cases > PSIM_FAIL_CASES) return PSIM_EINVAL;
+    const uint32_t nc = (uint32_t)n_cases;
+    const bool pl = h->cfg.manager == PSIM_MANAGER_PLUGGABLE;
+    if (h->hosted || (pl && h->cfg.strategy == PSIM_STRATEGY_FULL)) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
+    if (h->round_open) return PSIM_ESTATE;
+    const uint32_t N = h->N;
+    for (uint32_t j = 0; j < nc; j++)
+        if (cases[j].source >= N) return PSIM_ERANGE;
+    // the case table: k_rs_alive's, and the fanouts in its order
+    uint32_t ord[PSIM_FAIL_CASES], par[GO_PAR] = {0};
+    for (uint32_t j = 0; j < nc; j++) ord[j] = j;
+    std::stable_sort(ord, ord + nc, [&](uint32_t a, uint32_t b) { return cases[a].salt < cases[b].salt; });
+    for (uint32_t q = 0; q < nc; q++) {
+        const psim_gossip_case& c = cases[ord[q]];
+        par[RS_SRC + q] = c.source; par[RS_THR + q] = c.threshold; par[RS_SALT + q] = c.salt; par[RS_SLOT + q] = ord[q];
+        par[GO_FAN + q] = c.fanout;
+    }
+    hipStream_t st; const uint8_t* fl;
+    TRY(getter_begin(h, out, sizeof *out, st, fl));
+    // 1. the link set as rows, as psim_get_resilience reads it
+    LinkSet ls;
+    TmpBuf<unsigned long long> rs, go, alive, sel;
+    TmpBuf<uint32_t> dpar;
+    WordBfs b;
+    TRY(link_set(h, st, fl, ls));
+    // 2. the survivor words (they seed the BFS) and the chosen links
+    const uint32_t cap = level_cap(max_levels);
+    TRY(rs.alloc_on(RS_N, st)); TRY(go.alloc_on(GO_N, st)); TRY(dpar.alloc_on(GO_PAR, st));
+    TRY(alive.alloc_on(N, st)); TRY(b.seen.alloc_on(N, st)); TRY(b.front.alloc_on(N, st)); TRY(b.next.alloc_on(N, st));
+    TRY(sel.alloc_on(nc ? ls.slots : 0, st));
+    HIP_TRY(hipMemcpyAsync(dpar.p, par, sizeof par, hipMemcpyHostToDevice, st));
+    k_rs_live<<<1, 64, 0, st>>>(dpar.p, nc, fl, rs.p);
+    k_rs_alive<<<grid_for(N), BLK, 0, st>>>(dpar.p, nc, fail_seed, fl, N, rs.p, alive.p, b.seen.p, b.front.p);
+    if (nc) {
+        const unsigned long long all = nc == PSIM_FAIL_CASES ? ~0ull : (1ull << nc) - 1;
+        uint32_t fmin = PSIM_NONE;
+        for (uint32_t j = 0; j < nc; j++)
+            if (cases[j].fanout) fmin = std::min(fmin, cases[j].fanout);
+        k_go_select<<<grid_for(N), BLK, 0, st>>>(ls.ln, N, dpar.p, nc, fail_seed, all, fmin, sel.p);
+        if (pl)
+            k_go_select_long<<<grid_for((uint64_t)N * GO_LN), BLK, 0, st>>>(ls.ln, N, dpar.p, nc, fail_seed, all, fmin,
+                                                                          sel.p);
+    }
+    HIP_TRY(hipGetLastError());
+    unsigned long long rv[RS_N];
+    TRY(read_back(st, rv, rs.p, RS_N));
+    out->n_up = rv[RS_NUP];
+    const unsigned long long live = rv[RS_LIVE];
+    out->live_mask = live; out->cases_live = (uint64_t)__builtin_popcountll(live);
+    // 3. the BFS of psim_get_resilience, pushed over the chosen links only
+    if (live) {
+        TRY(b.lv.alloc_on(2 * ((size_t)cap + 1), st)); TRY(b.reach.alloc_on(PSIM_GRAPH_SOURCES, st));
+        unsigned long long prev[PSIM_FAIL_CASES] = {0}, cur[PSIM_FAIL_CASES] = {0};
+        const auto push = [&] {
+            k_go_push<<<grid_for(N), BLK, 0, st>>>(ls.ln, sel.p, N, b.front.p, b.seen.p, b.next.p);
+        };
+        TRY(bfs_levels(st, N, cap, b, cur, out, push, case_levels(out, cur, prev)));
+    }
+    // 4. the copies the senders pushed; with no live case only |L|
+    k_go_tally<<<grid_for(N), BLK, 0, st>>>(ls.ln, sel.p, N, alive.p, b.seen.p, b.front.p, go.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long gv[GO_N];
+    TRY(read_back(st, gv, go.p, GO_N));
+    out->links = gv[GO_L];
+    for (uint32_t j = 0; j < PSIM_FAIL_CASES; j++) {
+        out->alive[j] = gv[GO_ALIVE + j]; out->sent[j] = gv[GO_SENT + j]; out->lost[j] = gv[GO_LOST + j];
+    }
+    return PSIM_OK;
 }
 
 // a single-source BFS from the live node `root` over the rows k_tm_bfs reads,

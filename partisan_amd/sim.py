@@ -474,6 +474,33 @@ class Simulator(_Driver):
             out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
         return out
 
+    def gossip_reach(self, sources, fanouts, thresholds=None, salts=None, fail_seed=0, max_levels=0):
+        """Reach and cost of a gossip with a fanout under up to 64 cases
+        (psim_gossip_reach) as a dict of ints / arrays; a collective on rank
+        handles.  Case j starts at sources[j] after the failures of
+        resilience()'s case (sources[j], thresholds[j], salts[j]); every node
+        reached pushes once, to at most fanouts[j] of its links (0: to all of
+        them).  thresholds=None and salts=None mean all 0."""
+        src = np.ascontiguousarray(sources, np.uint32).reshape(-1)
+        cols = [src, np.ascontiguousarray(fanouts, np.uint32).reshape(-1)]
+        for v in (thresholds, salts):
+            cols.append(np.zeros(src.size, np.uint32) if v is None else np.ascontiguousarray(v, np.uint32).reshape(-1))
+        if any(c.size != src.size for c in cols):
+            raise ValueError("sources, fanouts, thresholds and salts differ in length")
+        cases = (_abi.PsimGossipCase * max(src.size, 1))()
+        for j in range(src.size):
+            cases[j].source, cases[j].fanout, cases[j].threshold, cases[j].salt = (int(c[j]) for c in cols)
+        m = _abi.PsimGossipReach()
+        self._check(self._extra["get_gossip_reach"](self._h, cases if src.size else None, src.size, int(fail_seed),
+                                                    max_levels, C.byref(m)), "get_gossip_reach")
+        out = {}
+        for name, _ in _abi.PsimGossipReach._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(m, name)
+            out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
+        return out
+
     # ---- the message trace (psim_trace_watch / psim_trace_read / psim_trace_clear)
     def trace_watch(self, nodes=None, to=True, frm=True, types=None, capacity=1 << 20):
         """Arm a watch: from the next round on, the records sent to (`to`) or
