@@ -3492,7 +3492,11 @@ static_assert(PSIM_QUARTER_WPB == WAVES_PER_BLOCK, "one block size for the bodie
 #endif
 constexpr uint32_t cmax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 constexpr uint32_t PHASE_LDS_WORDS = cmax(cmax(2 * S_N, ConsumeCarve::WORDS), cmax(lite::Carve<16>::WORDS, PtlCarve::WORDS));
+#if PSIM_LITE_ROWS_LDS        // (the lite carve with its Rows areas is the largest: 21,112 B)
+static_assert(PHASE_LDS_WORDS * 4 <= 40960, "k_hv_phase's LDS a block: four blocks of it per CU at 4 waves/SIMD");
+#else
 static_assert(PHASE_LDS_WORDS * 4 <= 19456, "k_hv_phase's LDS a block: no more than the three bodies' sum was");
+#endif
 __global__ void __launch_bounds__(64 * PSIM_QUARTER_WPB, PSIM_QUARTER_WAVES)
 k_hv_phase(RoundArgs args, const uint32_t sgrid, const uint32_t cgrid, const uint32_t egrid) {
     __shared__ __attribute__((aligned(16))) uint32_t pool[PHASE_LDS_WORDS];

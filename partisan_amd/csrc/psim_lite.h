@@ -70,6 +70,12 @@ namespace {
 #ifndef PSIM_QUARTER_WAVES
 #define PSIM_QUARTER_WAVES 4
 #endif
+// 1: the next node's rows reach LDS by LDS-DMA, issued before this node's
+// body (rows_dma / rows_read below); 0: by loads into registers issued after
+// the body, the text before it, for A/B (profiles/lite_rows_lds/ab_log.txt)
+#ifndef PSIM_LITE_ROWS_LDS
+#define PSIM_LITE_ROWS_LDS 1
+#endif
 #ifndef PSIM_QUARTER_STAGE    // (16 against 8: no difference, profiles/lite_quarter/ab_log.txt)
 #define PSIM_QUARTER_STAGE 8
 #endif
@@ -178,6 +184,10 @@ struct Lds {
     uint32_t* srec;                  // STAGE records x 16 words
     uint32_t* skey;                  // STAGE route keys
     uint32_t* scr;                   // SCR words of scratch
+#if PSIM_LITE_ROWS_LDS
+    uint32_t* rows;                  // the wave's Rows<W> area (one for its groups: a DMA's lanes are the wave's)
+    const uint32_t* tab;             // the block's table of the X4 DMA's pieces (rows_table)
+#endif
     typename Grp<W>::Magic KM;
 #ifdef PSIM_STAMPS
     unsigned long long* stl;         // 32 phase sums (LDS), shared by the wave's groups
@@ -679,6 +689,17 @@ DEV void merge_exchange(Node<W>& x, Lds<W>& w, uint32_t EX, uint32_t nex, bool s
 }
 
 // ---------------------------------------------------------- the node --
+// With the rows by LDS-DMA a register reloaded from scratch inside the body
+// costs the prefetch: scratch shares the in-order memory counter, so the wait
+// for the reload waits for the DMAs.  What the node loop's functions derive
+// from the lane id alone (an address offset such as 4 (l & 7), as 64 bits) the
+// compiler hoists out of the loop and then spills; PER_NODE(l) has it worked
+// out again per node instead, a VALU operation or two.
+#if PSIM_LITE_ROWS_LDS
+#define PER_NODE(l) asm volatile("" : "+v"(l))
+#else
+#define PER_NODE(l) do { } while (0)
+#endif
 // inputs of a group's node: its descriptor, header words, rows, the first
 // inbox records (all lanes of a group load the same addresses, or their own
 // element of a row)
@@ -713,10 +734,106 @@ DEV void load_rows(KArgs& a, In<W>& in, bool live) {
     in.cm = a.lite_cm[li];
     in.oe = reinterpret_cast<const uint32_t*>(a.obase + li + 1)[0];   // (totals < 2^32 slots)
 }
+#if PSIM_LITE_ROWS_LDS
+// The same rows by LDS-DMA (global_load_lds: a load with no destination
+// register), so that the next node's can be issued BEFORE this node's body
+// and land while it runs, holding no VGPR across it -- and with them the
+// descriptor of the node after that one, whose load-and-wait otherwise sits
+// behind the writeback's stores on the one in-order memory counter.  A DMA
+// writes LDS at a wave-uniform base + lane x size, whatever the exec mask: the
+// area is laid out by lane and is the wave's, and a group that has left the
+// loop simply leaves its entries unwritten.
+// Three DMAs a node, in words from the wave's area:
+//   X4   one 16-B piece a lane -- a group's lanes at W * 4 * its index:
+//          lanes 0-7   the passive row's eight pieces        words  0-31
+//          lanes 8-9   the active row's two                         32-39
+//          lanes 10-11 header words 0-3 (0, 1: the draw counter)    40-43
+//                      and 8-11 (9: the view sizes)                 44-47
+//          lane 12     obase[row], obase[row + 1]                   48-51
+//          lanes 13..  the descriptor of the node after             52-55, ...
+//        so a lane reads back its share of the passive row as from the row
+//        itself (Pas<W>::load), its active entry and the group-uniform words
+//   CM   lite_cm[row], 2 B zero-extended to the lane's own word: every lane of
+//        the group fetches it, and reads back its own copy
+//   PT   the partition byte, 1 B, likewise
+// (a sub-word DMA writes a word a lane, as the load does a register.)  Every
+// piece lies inside its array: no over-read of an aligned-down word.
+template <uint32_t W>
+struct Rows {
+    static constexpr uint32_t X4 = 0, CM = 64 * 4, PT = CM + 64, WORDS = PT + 64;   // a wave's
+    static constexpr uint32_t PAS = 0, ACT = 32, H0 = 40, H9 = 45, OE = 50, DESC = 52;   // in a group's X4 words
+    static_assert(DESC + 4 <= W * 4, "a group's pieces: 14 lanes of its W");
+};
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef const __attribute__((address_space(1))) void* glb_ptr_t;
+// A lane's piece of the X4 DMA is base + (index << shift): the block's table
+// (Carve::TAB, filled once by rows_table) holds for lane l of a group
+// {base (the piece's offset in the row added), shift = log2 of the array's row
+// bytes, 1 where the index is the list entry and not the node's row}.  In
+// registers these would be four VGPRs live -- or spilled -- across the whole
+// loop, and worked out per node a chain of selects over five pointers.
+template <uint32_t W>
+DEV void rows_table(KArgs& a, uint32_t* tab) {
+    static_assert(PSIM_PASSIVE_CAP * 4 == 1 << 7 && PSIM_ACTIVE_CAP * 4 == 1 << 5 && sizeof(Hdr) == 1 << 6 &&
+                  sizeof(*a.obase) == 1 << 3 && sizeof(*a.desc_lite) == 1 << 4, "the shifts below");
+    for (uint32_t l = threadIdx.x; l < W; l += blockDim.x) {
+        uint64_t b;
+        uint32_t sh;
+        if (l < 8) { b = (uint64_t)a.pas + l * 16; sh = 7; }
+        else if (l < 10) { b = (uint64_t)a.act + (l - 8) * 16; sh = 5; }
+        else if (l < 12) { b = (uint64_t)a.hdr + (l - 10) * 32; sh = 6; }
+        else if (l < 13) { b = (uint64_t)a.obase; sh = 3; }
+        else { b = (uint64_t)a.desc_lite; sh = 4; }
+        tab[4 * l] = (uint32_t)b; tab[4 * l + 1] = (uint32_t)(b >> 32);
+        tab[4 * l + 2] = sh; tab[4 * l + 3] = l < 13 ? 0u : 1u;
+    }
+}
+// Issue the DMAs: the rows of the node of descriptor D (row 0 for a group
+// without one: the result is unused) and entry `dn` of the list.  The caller
+// has waited for the area's last reads.
+// (`lid`: the lane id, laundered per node by the caller so that what is
+// derived from it -- here and in rows_read -- is recomputed per node, a few
+// VALU operations, and not hoisted out of the loop into registers held, or
+// spilled, across the body: a reload after the writeback's stores waits for
+// them.)
+template <uint32_t W>
+DEV void rows_dma(KArgs& a, const Lds<W>& w, uint32_t lid, const uint4& D, bool live, uint32_t dn) {
+    using R = Rows<W>;
+    const uint32_t li = live ? D.x - a.lo : 0u;
+    const uint4 t = reinterpret_cast<const uint4*>(w.tab)[lid & (W - 1)];
+    const uint64_t src = (((uint64_t)t.y << 32) | t.x) + ((uint64_t)(t.w ? dn : li) << t.z);
+    __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)(w.rows + R::X4), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_ptr_t)(a.lite_cm + li), (lds_ptr_t)(w.rows + R::CM), 2, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_ptr_t)(a.part + (live ? D.x : 0u)), (lds_ptr_t)(w.rows + R::PT), 1, 0, 0);
+}
+// the landed rows into `in` (after the wait for the DMAs)
+template <uint32_t W>
+DEV void rows_read(const Lds<W>& w, uint32_t lid, In<W>& in) {
+    using R = Rows<W>;
+    const uint32_t l = lid & (W - 1);
+    const uint32_t* const g = w.rows + R::X4 + (lid & (64 - W)) * 4;   // the group's W * 4 words
+    in.r0 = g[R::H0]; in.r1 = g[R::H0 + 1]; in.w9 = g[R::H9];
+    in.A = g[R::ACT + (l & (PSIM_ACTIVE_CAP - 1))];
+    in.A = l < PSIM_ACTIVE_CAP ? in.A : 0u;
+    in.P = reinterpret_cast<const typename Pas<W>::Row*>(g + R::PAS)[l];    // (as Pas<W>::load of the row)
+    in.oe = g[R::OE];                                                  // (totals < 2^32 slots)
+    in.cm = w.rows[R::CM + lid] & 0xFFFFu;
+    in.part = w.rows[R::PT + lid] & 0xFFu;
+}
+
+// the landed descriptor (zeros for a group without that node)
+template <uint32_t W>
+DEV uint4 desc_read(const Lds<W>& w, uint32_t lid, bool live) {
+    using R = Rows<W>;
+    const uint4 d = *reinterpret_cast<const uint4*>(w.rows + R::X4 + (lid & (64 - W)) * 4 + R::DESC);
+    return live ? d : make_uint4(0, 0, 0, 0);
+}
+#endif
 // the descriptor's inbox heads (issued a node ahead)
 template <uint32_t W>
 DEV In<W> load_in(KArgs& a, const uint4& D) {
-    const uint32_t l = Grp<W>::lane();
+    uint32_t l = Grp<W>::lane();
+    PER_NODE(l);
     In<W> in;
     in.D = D;
     in.r0 = in.r1 = in.w9 = in.A = in.part = in.cm = in.oe = 0;
@@ -753,7 +870,8 @@ template <uint32_t W>
 DEV void body(Node<W>& x, Lds<W>& w, Cnt& c, const In<W>& in) {
     using G = Grp<W>;
     KArgs& a = kargs();
-    const uint32_t l = G::lane();
+    uint32_t l = G::lane();
+    PER_NODE(l);
     // the inbox in canonical order, W records at a time: lane l holds record
     // cb + l's sender and type word, and the loop visits the HyParView
     // records among them (Plumtree ones are k_ptl's)
@@ -854,7 +972,17 @@ template <uint32_t W>
 struct Carve {
     using G = Grp<W>;
     static constexpr uint32_t SREC = (NST * 2 + 3) & ~3u, SKEY = SREC + G::WPB * G::N * G::STAGE * 16,
-                              SCR = SKEY + G::WPB * G::N * G::STAGE, WORDS = SCR + G::WPB * G::N * G::SCR;
+                              SCR = SKEY + G::WPB * G::N * G::STAGE,
+#if PSIM_LITE_ROWS_LDS        // ... then per wave the Rows<W> area of the next node's rows
+                              // and the block's table of the pieces (rows_table)
+                              ROWS = SCR + G::WPB * G::N * G::SCR, TAB = ROWS + G::WPB * Rows<W>::WORDS,
+                              WORDS = TAB + W * 4;
+    static_assert(ROWS % 4 == 0 && TAB % 4 == 0, "the DMA's 16-B pieces, the table's 16-B entries");
+#else
+                              WORDS = SCR + G::WPB * G::N * G::SCR;
+#endif
+    // four blocks a CU stay resident (4 waves/SIMD in blocks of four waves): 160 KiB / 4
+    static_assert(WORDS * 4 <= 40960, "the block's LDS: four blocks of it per CU at 4 waves/SIMD");
 };
 // Block `bid` of `nblk`: the launch's own index and grid in k_lite_quarter /
 // k_lite_half, the lite range's in k_hv_phase (psim_consume.hip).
@@ -883,6 +1011,9 @@ DEV void lite_kernel(const uint32_t bid, const uint32_t nblk, uint32_t* const po
     for (int i = threadIdx.x; i < (int)(WPB * 32); i += blockDim.x) (&stls[0][0])[i] = 0;
 #endif
     for (int i = threadIdx.x; i < NST; i += blockDim.x) sst[i] = 0;
+#if PSIM_LITE_ROWS_LDS
+    rows_table<W>(kargs(), pool + Carve<W>::TAB);
+#endif
     __syncthreads();
     const uint32_t wid = threadIdx.x >> 6, g = G::idx();
     Lds<W> w;
@@ -902,6 +1033,58 @@ DEV void lite_kernel(const uint32_t bid, const uint32_t nblk, uint32_t* const po
     const uint32_t step = G::N * nw;
     uint32_t lc[4], na;
     lite_counts(kargs(), lc, na);
+#if PSIM_LITE_ROWS_LDS        // (the list's counts are wave-uniform: in SGPRs, not in VGPRs that spill)
+    for (uint32_t k = 0; k < 4; k++) lc[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)lc[k]);
+    na = lc[0] + lc[1] + lc[2] + lc[3];
+    // (the area's base is wave-uniform: the DMAs' M0)
+    w.rows = pool + Carve<W>::ROWS + (uint32_t)__builtin_amdgcn_readfirstlane((int)wid) * Rows<W>::WORDS;
+    w.tab = pool + Carve<W>::TAB;
+    // The memory counter (vmcnt) is one, in order, for loads, DMAs and stores,
+    // and the waits on the DMAs are this loop's own:
+    //   top     the area's reads of node i, which begin() consumes; the inbox
+    //           heads of node i + 1 (ordinary loads, as before); a wait for
+    //           the reads (lgkmcnt) and then the DMAs of node i + 1's rows and
+    //           node i + 2's descriptor, which overwrite the area
+    //   body    the DMAs land behind it.  An ordinary load's result used in it
+    //           (an inbox past W records, an exchange past PREF, connect_ok's
+    //           pair) waits for the DMAs too: correct, and rare
+    //   end     one wait for everything, before the writeback's stores; the
+    //           inbox heads are taken here (`pin`), since a use the compiler
+    //           sinks past the stores waits for those too, and the descriptor
+    //           is read from the area
+    // so that nothing waits on the stores but the next node's end-of-body wait.
+    if (first < na) {
+        Node<W> x;
+        In<W> in = load_in<W>(kargs(), load_desc(kargs(), lc, first, true));
+        rows_dma(kargs(), w, __lane_id(), in.D, true, lite_at(kargs(), lc, first + step < na ? first + step : first));
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        uint4 Dn = desc_read(w, __lane_id(), first + step < na);
+        for (uint32_t i = first; i < na; i += step) {
+            LSTAMP(w, 8);
+            uint32_t lid = __lane_id();
+            PER_NODE(lid);
+            rows_read(w, lid, in);
+            begin(x, in);
+            // the connection bits and the outbox bound, fetched with the rows
+            x.AF = (in.cm & 0xFFu) | (min(in.oe - x.ob, 0xFFFFFFu) << 8);
+            // the next node's inputs, in flight while this one runs
+            const uint32_t nx = i + step, nnx = i + 2 * step;
+            In<W> inn = load_in<W>(kargs(), Dn);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            rows_dma(kargs(), w, lid, Dn, nx < na, lite_at(kargs(), lc, nnx < na ? nnx : i));
+            LSTAMP(w, 0);
+            body(x, w, c, in);
+            LSTAMP(w, 9);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            asm volatile("" : "+v"(inn.SRC), "+v"(inn.TT), "+v"(inn.EXP));   // pin
+            Dn = desc_read(w, lid, nnx < na);
+            writeback(x, w, c);
+            LSTAMP(w, 7);
+            in = inn;
+        }
+        count(w, c);
+    }
+#else
     if (first < na) {
         Node<W> x;
         In<W> in = load_in<W>(kargs(), load_desc(kargs(), lc, first, true));
@@ -926,6 +1109,7 @@ DEV void lite_kernel(const uint32_t bid, const uint32_t nblk, uint32_t* const po
         }
         count(w, c);
     }
+#endif
     // the digest partials of every lane
     {
         uint64_t dg = c.digest;
