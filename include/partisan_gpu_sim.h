@@ -558,6 +558,86 @@ typedef struct psim_gossip_reach {
     uint64_t reserved[8];
 } psim_gossip_reach;
 
+/* Transitive unicast over the overlay, computed on the device (DESIGN.md
+ * "Transitive unicast"): what a forward_message with {broadcast, true} and
+ * {transitive, true} does under the HyParView manager -- the
+ * {relay_message, Node, Message, TTL} flood down the "tree" out-links
+ * (hyparview:1138-1163, :1274-1343, :1800-1868, :563-570) -- over the frozen
+ * state, up to PSIM_RELAY_CASES (source, target, ttl) cases at once.  Nothing
+ * deduplicates, so the flood counts walks: a level holds entries (node v,
+ * remaining ttl t) -> c copies.  Everything is an integer, so the struct is
+ * bit-exact whatever the order of any sum.
+ *   Node p is live if p < n_nodes and node p is up.  Liveness is the only
+ *     filter: partitions are ignored, as in every statistics call.
+ *   state(i, p) for a live i, p != i and p live, from act and conn of
+ *     psim_node_view, decided in this order: conn(i) holds p | PSIM_CONN_DOWN:
+ *     `down` if p is in act(i), otherwise `none`; conn(i) holds plain p (a
+ *     lingering peer): `connected`; p is in act(i): `connected`; otherwise
+ *     `none` -- also for p == i or p not live.
+ *   out(i): the entries e of pt_common[0 .. pt_common_n) with e != i -- the
+ *     atom self is what `-- [node()]` removes; retrieve_outlinks/0 asks with
+ *     the atom root, so all_peers/3 (pt:627-631) always answers common_eagers,
+ *     never a per-root set.  Each entry is one send, to p = e & ~PSIM_MAP_BIT.
+ *   The census, over live i: out_entries = the sum of |out(i)|; out_usable its
+ *     entries with state(i, p) `connected`; out_nonmember its entries whose p
+ *     is not in act(i); members_down the pairs (i, p), p in act(i), with
+ *     state(i, p) `down`; out_degree bins the live nodes by their usable
+ *     entries (bin k = value k, the last bin = PSIM_HIST_BINS - 1 or more).
+ *   Case j = (s, d, T) is live if s and d are both live; a case that is not
+ *     is skipped and its slots stay zero.
+ *   Origin: state(s, d) `connected`: the send is direct -- bit j of
+ *     direct_mask, delivered = first_hop = hop_sum = 1 and nothing else.
+ *     Otherwise s runs forward(s, T, 1).
+ *   forward(v, t, c): for each e of out(v): state(v, p) `connected`: relays +=
+ *     c, and c copies arrive at (p, t - 1) on the next level; otherwise
+ *     refused += c.
+ *   Level l = 1, 2, ... takes the merged entries (v, t) -> c of that level:
+ *     d in act(v) and state(v, d) `connected`: delivered += c, hop_sum +=
+ *     c (l + 1), first_hop = l + 1 if it is still 0; d in act(v) with any
+ *     other state: restarts += c and forward(v, T, c) -- do_send_message with
+ *     {transitive, true} and no connection starts a new tree forward with a
+ *     fresh ttl (hv:1150, :1289-1295, :1323-1335); d not in act(v) and t == 0:
+ *     expired += c; otherwise forward(v, t, c).
+ *   Levels run while l <= the level cap.  levels[j]: the last level run that
+ *     had entries of case j; peak[j]: the most distinct (v, t) entries of the
+ *     case on one level run.  If level cap + 1 would have entries of case j,
+ *     bit j of truncated_mask is set and in_flight[j] is the sum of their
+ *     counts (copies already counted in relays).
+ *   pt_common holds at most PSIM_PT_MEMBERS_CAP = 8 entries, so no count
+ *     exceeds 8^16 = 2^48 and no sum overflows. */
+#define PSIM_RELAY_CASES 64
+#define PSIM_RELAY_MAX_TTL 16      /* also the level cap's maximum */
+typedef struct psim_relay_case {
+    uint32_t source;     /* the node that calls forward_message */
+    uint32_t target;     /* the node the message is for; != source */
+    uint32_t ttl;        /* 1 .. PSIM_RELAY_MAX_TTL; the reference's RELAY_TTL is 5 (partisan.hrl:9) */
+    uint32_t reserved;   /* 0 */
+} psim_relay_case;
+typedef struct psim_relay_reach {
+    uint64_t n_up;                           /* live nodes */
+    uint64_t out_entries;                    /* sum of |out(i)| */
+    uint64_t out_usable;                     /* ... with state `connected` */
+    uint64_t out_nonmember;                  /* ... whose p is not in act(i): stale entries */
+    uint64_t members_down;                   /* (i, p), p in act(i), state `down` */
+    uint64_t out_degree[PSIM_HIST_BINS];     /* live nodes by usable out entries */
+    uint64_t cases_live;                     /* number of live cases */
+    uint64_t live_mask;                      /* bit j set: case j is live */
+    uint64_t direct_mask;                    /* bit j set: the source holds a connection to the target */
+    uint64_t truncated_mask;                 /* bit j set: the level cap ended case j with copies in flight */
+    uint64_t levels_max;                     /* the largest levels[j] */
+    uint64_t delivered[PSIM_RELAY_CASES];    /* copies handed to the target */
+    uint64_t first_hop[PSIM_RELAY_CASES];    /* sends on the shortest delivering walk, 0: none */
+    uint64_t hop_sum[PSIM_RELAY_CASES];      /* sends summed over the delivered copies */
+    uint64_t relays[PSIM_RELAY_CASES];       /* relay_message sends */
+    uint64_t refused[PSIM_RELAY_CASES];      /* sends to an out entry without a connection */
+    uint64_t expired[PSIM_RELAY_CASES];      /* copies dropped at ttl 0 */
+    uint64_t restarts[PSIM_RELAY_CASES];     /* copies whose holder restarted the flood with a fresh ttl */
+    uint64_t in_flight[PSIM_RELAY_CASES];    /* copies the level cap cut off */
+    uint64_t levels[PSIM_RELAY_CASES];       /* the last level that had entries */
+    uint64_t peak[PSIM_RELAY_CASES];         /* the most distinct (v, t) entries on one level */
+    uint64_t reserved[8];
+} psim_relay_reach;
+
 typedef struct psim_handle psim_handle;
 
 void psim_default_config(psim_config *cfg);
@@ -754,6 +834,25 @@ int psim_get_resilience(psim_handle *h, const psim_failure_case *cases, size_t n
  * same struct).  No Erlang binding yet. */
 int psim_get_gossip_reach(psim_handle *h, const psim_gossip_case *cases, size_t n_cases, uint64_t fail_seed,
                           uint32_t max_levels, psim_gossip_reach *out);
+/* Transitive unicasts over up to PSIM_RELAY_CASES (source, target, ttl) cases
+ * (psim_relay_reach above), on the device, for HyParView handles with
+ * Plumtree, of any shard count; slot j of every per-case array is cases[j].
+ * Two cases may name the same pair.  n_cases == 0 fills the census only.
+ * max_levels caps the levels: 0 means PSIM_RELAY_MAX_TTL, and larger values
+ * are clamped to it.  Errors, in this order: PSIM_EINVAL for a null h or out,
+ * null cases with n_cases > 0, n_cases > PSIM_RELAY_CASES, a non-zero
+ * `reserved`, a ttl of 0 (the reference loops forever on it) or above
+ * PSIM_RELAY_MAX_TTL, or source == target; PSIM_EUNSUPPORTED for pluggable,
+ * X-BOT (its relay_message/3 carries no ttl, xbot:1157-1161: another rule) and
+ * host-exchange handles and plumtree = 0; PSIM_ESTATE with a round open;
+ * PSIM_ERANGE for a source or target >= n_nodes (a dead one is legal: the case
+ * is skipped); PSIM_ENOMEM if the temporaries of the frontier cannot be had
+ * (the handle stays usable).  Read-only: the rounds stepped after it are those
+ * of a run without it.  A collective on rank handles (every rank calls with
+ * the same arguments; every rank gets the same struct).  No Erlang binding yet
+ * (INTEGRATION.md). */
+int psim_get_relay_reach(psim_handle *h, const psim_relay_case *cases, size_t n_cases, uint32_t max_levels,
+                         psim_relay_reach *out);
 /* Snapshot of the whole simulation state of this process (node rows,
  * in-flight messages, round, events not yet applied are not included):
  * with buf == NULL (or cap too small) only *need is set.  psim_restore

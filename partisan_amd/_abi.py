@@ -209,6 +209,29 @@ class PsimGossipReach(C.Structure):
     ]
 
 
+RELAY_CASES, RELAY_MAX_TTL = 64, 16
+
+
+class PsimRelayCase(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("target", C.c_uint32), ("ttl", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PsimRelayReach(C.Structure):
+    _fields_ = [
+        ("n_up", C.c_uint64), ("out_entries", C.c_uint64), ("out_usable", C.c_uint64),
+        ("out_nonmember", C.c_uint64), ("members_down", C.c_uint64),
+        ("out_degree", C.c_uint64 * HIST_BINS),
+        ("cases_live", C.c_uint64), ("live_mask", C.c_uint64), ("direct_mask", C.c_uint64),
+        ("truncated_mask", C.c_uint64), ("levels_max", C.c_uint64),
+        ("delivered", C.c_uint64 * RELAY_CASES), ("first_hop", C.c_uint64 * RELAY_CASES),
+        ("hop_sum", C.c_uint64 * RELAY_CASES), ("relays", C.c_uint64 * RELAY_CASES),
+        ("refused", C.c_uint64 * RELAY_CASES), ("expired", C.c_uint64 * RELAY_CASES),
+        ("restarts", C.c_uint64 * RELAY_CASES), ("in_flight", C.c_uint64 * RELAY_CASES),
+        ("levels", C.c_uint64 * RELAY_CASES), ("peak", C.c_uint64 * RELAY_CASES),
+        ("reserved", C.c_uint64 * 8),
+    ]
+
+
 NODE_VIEW_DTYPE = np.dtype(PsimNodeView)
 STRATEGY_VIEW_DTYPE = np.dtype(PsimStrategyView)
 STATS_DTYPE = np.dtype(PsimRoundStats)
@@ -264,6 +287,7 @@ GPU_ONLY = {
                                  C.POINTER(PsimResilience)]),
     "get_gossip_reach": (C.c_int, [_H, C.POINTER(PsimGossipCase), C.c_size_t, C.c_uint64, C.c_uint32,
                                    C.POINTER(PsimGossipReach)]),
+    "get_relay_reach": (C.c_int, [_H, C.POINTER(PsimRelayCase), C.c_size_t, C.c_uint32, C.POINTER(PsimRelayReach)]),
     # the message trace (no oracle twin: the tests filter Oracle.inbox())
     "trace_watch": (C.c_int, [_H, _P32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_size_t]),
     "trace_read": (C.c_int, [_H, _P32, _P32, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),

@@ -1,4 +1,4 @@
-// psim_metrics.hip -- the read-only analyses of the overlay behind six
+// psim_metrics.hip -- the read-only analyses of the overlay behind seven
 // getters of include/partisan_gpu_sim.h; no round runs any of it:
 //   psim_get_histograms           HyParView's views, the tracked broadcast, components
 //   psim_get_strategy_histograms  the pluggable strategies' views (SCAMP's as a CSR)
@@ -6,6 +6,7 @@
 //   psim_get_resilience           that BFS over 64 mass-failure cases
 //   psim_get_gossip_reach         ... pushed over at most `fanout` links a node
 //   psim_get_tree_metrics         a Plumtree root's eager tree against the overlay
+//   psim_get_relay_reach          the transitive unicast's relay flood, 64 cases
 // Each waits for every shard's stream, works on the first shard's, and is a
 // collective on ranks.  Shared by the analyses: Links (a link set as rows) and
 // link_set (its host side), bfs_levels (the word BFS's level loop), wave_or /
@@ -1195,6 +1196,287 @@ __global__ void __launch_bounds__(BLK) k_tm_final(const uint32_t* __restrict__ i
         if (sh[j]) atomicAdd(&tf[j], sh[j]);
 }
 
+// -------------------------------------------------- transitive unicast --
+// psim_get_relay_reach (psim_relay_reach in the header defines every field):
+// the relay_message flood counts walks, so its frontier is a sparse list of
+// (case, ttl, node) -> count entries instead of a word per node.
+//   k_rl_pack     virtual shards and ranks: a node's three rows and their
+//                 lengths by global id (one shard reads its rows in place)
+//   k_rl_census   16 lanes a node: the out entries in lanes 0-7, the active
+//                 view in lanes 8-15, the connection table in both halves;
+//                 every entry meets every other by a shuffle in its group
+//   k_rl_expand   a level's entries: LN = 1, a lane an entry, the rows in
+//                 registers, or LN = 8 lanes an entry, lane g out-link g and
+//                 entry g of each row (PSIM_RELAY_LANES=8, for A/B: the
+//                 slower of the two); per-case tallies into the
+//                 block's LDS tile, the children at a block-wide offset
+//   k_rl_merge    the children into an open-addressing table: the key claimed
+//                 by a 64-bit atomicCAS, the count added by a 64-bit atomicAdd
+//   k_rl_compact  the table's used slots -> the next level's entries, their
+//                 number and count sum per case
+// A key: case << 32 | ttl << 27 | node.  The case table `par`: RP_DST, RP_TTL.
+enum { RC_NUP = 0, RC_ENT, RC_USE, RC_NONMEM, RC_DOWN, RC_DEG, RC_N = RC_DEG + PSIM_HIST_BINS };
+enum { RF_DELIV = 0, RF_HOPS, RF_RELAY, RF_REFUSED, RF_EXPIRED, RF_RESTART, RF_FIRST, RF_FIELDS,
+       RF_LIVE = RF_FIELDS * PSIM_RELAY_CASES, RF_DIRECT, RF_N };
+enum { RP_DST = 0, RP_TTL = PSIM_RELAY_CASES, RP_N = 2 * PSIM_RELAY_CASES };
+enum { RV_CHILD = 0, RV_NEXT, RV_DISTINCT, RV_SUM = RV_DISTINCT + PSIM_RELAY_CASES, RV_N = RV_SUM + PSIM_RELAY_CASES };
+enum : uint32_t { RL_NONE = 0, RL_CONN = 1, RL_DOWN = 2 };
+constexpr unsigned long long RL_EMPTY = ~0ull;
+constexpr uint32_t RL_ROW = 8;
+static_assert(PSIM_ACTIVE_CAP == RL_ROW && PSIM_PT_MEMBERS_CAP == RL_ROW && PSIM_CONN_CAP == RL_ROW,
+              "three rows of 8 words: one 8-lane group holds each");
+static_assert(PSIM_RELAY_MAX_TTL < 32 && KEY_DST_BITS == 27, "a key: 6 bits of case, 5 of ttl, 27 of node");
+
+struct RlRows {
+    const Hdr* hdr;            // one shard: the lengths in place; else nullptr and cnt
+    const uint32_t* cnt;       // act_n | com_n << 8 | conn_n << 16 by global id
+    const uint32_t *act, *com, *conn;
+    // the three lengths, each at most RL_ROW
+    DEV void counts(uint32_t i, uint32_t& an, uint32_t& en, uint32_t& kn) const {
+        if (hdr) { an = hdr[i].act_n; en = hdr[i].com_n; kn = hdr[i].conn_n; }
+        else { const uint32_t c = cnt[i]; an = c & 0xFFu; en = (c >> 8) & 0xFFu; kn = (c >> 16) & 0xFFu; }
+        an = min(an, RL_ROW); en = min(en, RL_ROW); kn = min(kn, RL_ROW);
+    }
+};
+
+DEV unsigned long long rl_key(uint32_t j, uint32_t ttl, uint32_t node) {
+    return ((unsigned long long)j << 32) | ((unsigned long long)ttl << KEY_DST_BITS) | node;
+}
+// state(i, p) of a live p != i from what the rows of i hold
+DEV uint32_t rl_state(bool live, bool in_act, bool down, bool plain) {
+    return !live ? RL_NONE : down ? (in_act ? RL_DOWN : RL_NONE) : (plain || in_act ? RL_CONN : RL_NONE);
+}
+DEV bool rl_live(const uint8_t* __restrict__ flags, uint32_t N, uint32_t i, uint32_t p) {
+    return p != i && p < N && (flags[p] & F_UP);
+}
+
+__global__ void k_rl_pack(const Hdr* __restrict__ hdr, const uint32_t* __restrict__ act,
+                          const uint32_t* __restrict__ com, const uint32_t* __restrict__ conn, uint32_t n,
+                          uint32_t* gact, uint32_t* gcom, uint32_t* gconn, uint32_t* gcnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    gcnt[i] = (uint32_t)hdr[i].act_n | (uint32_t)hdr[i].com_n << 8 | (uint32_t)hdr[i].conn_n << 16;
+    for (uint32_t q = 0; q < RL_ROW; q++) {
+        gact[(size_t)i * RL_ROW + q] = act[(size_t)i * RL_ROW + q];
+        gcom[(size_t)i * RL_ROW + q] = com[(size_t)i * RL_ROW + q];
+        gconn[(size_t)i * RL_ROW + q] = conn[(size_t)i * RL_ROW + q];
+    }
+}
+
+// (over the whole overlay's rows, the same on every rank: nothing to reduce)
+__global__ void __launch_bounds__(BLK) k_rl_census(RlRows R, const uint8_t* __restrict__ flags, uint32_t N,
+                                                   unsigned long long* cs) {
+    constexpr uint32_t LN = 16;
+    __shared__ unsigned long long sh[RC_N];
+    for (uint32_t j = threadIdx.x; j < RC_N; j += blockDim.x) sh[j] = 0;
+    __syncthreads();
+    const uint32_t l = lane_id(), g = l % LN, gb = l - g, q8 = g % RL_ROW;
+    const uint32_t i = (blockIdx.x * BLK + threadIdx.x) / LN;
+    const bool up = i < N && (flags[i] & F_UP), is_out = g < RL_ROW;
+    uint32_t x = PSIM_NONE, cn = PSIM_NONE;            // the lane's out or active entry; its connection entry
+    bool valid = false;
+    if (up) {
+        uint32_t an, en, kn;
+        R.counts(i, an, en, kn);
+        valid = q8 < (is_out ? en : an);
+        if (valid) x = (is_out ? R.com : R.act)[(size_t)i * RL_ROW + q8];
+        if (q8 < kn) cn = R.conn[(size_t)i * RL_ROW + q8];
+    }
+    const uint32_t p = is_out ? x & ~PSIM_MAP_BIT : x;
+    bool in_act = false, dn = false, pl = false, dup = false;
+#pragma unroll
+    for (uint32_t q = 0; q < RL_ROW; q++) {            // (every lane of the wave: no branch around a shuffle)
+        const uint32_t aq = shfl(x, (int)(gb + RL_ROW + q)), cq = shfl(cn, (int)(gb + q));
+        in_act |= aq == p; dn |= cq == (p | PSIM_CONN_DOWN); pl |= cq == p;
+        dup |= q < q8 && aq == p;                      // (read by the active lanes only)
+    }
+    const uint32_t st = rl_state(valid && rl_live(flags, N, i, p), in_act, dn, pl);
+    const bool ent = valid && is_out && x != i;
+    const uint64_t b_ent = ballot(ent), b_use = ballot(ent && st == RL_CONN), b_non = ballot(ent && !in_act);
+    const uint64_t b_dn = ballot(valid && !is_out && !dup && st == RL_DOWN), b_up = ballot(up && g == 0);
+    if (up && g == 0) atomicAdd(&sh[RC_DEG + hbin(popc((b_use >> gb) & 0xFFFFull))], 1ull);
+    if (l == 0) {
+        if (b_up) atomicAdd(&sh[RC_NUP], (unsigned long long)popc(b_up));
+        if (b_ent) atomicAdd(&sh[RC_ENT], (unsigned long long)popc(b_ent));
+        if (b_use) atomicAdd(&sh[RC_USE], (unsigned long long)popc(b_use));
+        if (b_non) atomicAdd(&sh[RC_NONMEM], (unsigned long long)popc(b_non));
+        if (b_dn) atomicAdd(&sh[RC_DOWN], (unsigned long long)popc(b_dn));
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < RC_N; j += blockDim.x)
+        if (sh[j]) atomicAdd(&cs[j], sh[j]);
+}
+
+// what an entry (case j, ttl tt, node v) -> c does at level lvl (0: the origin)
+// once its node's rows are known: d_act / d_conn: the target is an active
+// member of v / state(v, d) is connected.  Returns whether v forwards, and
+// with which ttl; the entry's own tallies go into the block's tile
+DEV bool rl_decide(unsigned long long* sh, unsigned long long* tl, uint32_t j, uint32_t tt, uint32_t T,
+                   unsigned long long c, uint32_t lvl, bool d_act, bool d_conn, uint32_t& ft) {
+    ft = tt;
+    if (lvl == 0) {
+        atomicOr(&tl[RF_LIVE], 1ull << j);
+        if (d_conn) atomicOr(&tl[RF_DIRECT], 1ull << j);
+    }
+    if (lvl == 0 ? d_conn : d_act && d_conn) {
+        atomicAdd(&sh[RF_DELIV * PSIM_RELAY_CASES + j], c);
+        atomicAdd(&sh[RF_HOPS * PSIM_RELAY_CASES + j], c * (lvl + 1));
+        atomicMin(&sh[RF_FIRST * PSIM_RELAY_CASES + j], (unsigned long long)(lvl + 1));
+        return false;
+    }
+    if (lvl == 0) return true;
+    if (d_act) {
+        atomicAdd(&sh[RF_RESTART * PSIM_RELAY_CASES + j], c);
+        ft = T;
+        return true;
+    }
+    if (tt == 0) {
+        atomicAdd(&sh[RF_EXPIRED * PSIM_RELAY_CASES + j], c);
+        return false;
+    }
+    return true;
+}
+
+template <uint32_t LN>
+__global__ void __launch_bounds__(BLK) k_rl_expand(RlRows R, const uint8_t* __restrict__ flags, uint32_t N,
+                                                   const uint32_t* __restrict__ par,
+                                                   const unsigned long long* __restrict__ fkey,
+                                                   const unsigned long long* __restrict__ fcnt, uint64_t nf,
+                                                   uint32_t lvl, unsigned long long* ckey,
+                                                   unsigned long long* ccnt, unsigned long long* rv,
+                                                   unsigned long long* tl) {
+    static_assert(LN == RL_ROW || LN == 1, "a group a row, or a lane an entry");
+    __shared__ unsigned long long sh[RF_FIELDS * PSIM_RELAY_CASES];
+    __shared__ unsigned long long sh_base;
+    for (uint32_t q = threadIdx.x; q < RF_FIELDS * PSIM_RELAY_CASES; q += blockDim.x)
+        sh[q] = q / PSIM_RELAY_CASES == RF_FIRST ? RL_EMPTY : 0ull;
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * BLK + threadIdx.x, ei = t / LN;
+    const uint32_t l = lane_id(), g = (uint32_t)(t % LN), gb = l - g;
+    bool on = ei < nf;
+    const unsigned long long key = on ? fkey[ei] : 0ull, c = on ? fcnt[ei] : 0ull;
+    const uint32_t j = (uint32_t)(key >> 32), tt = (uint32_t)(key >> KEY_DST_BITS) & 31u, v = (uint32_t)key & KEY_DST_MASK;
+    const uint32_t d = par[RP_DST + j], T = par[RP_TTL + j];
+    // (the origin: a case whose source or target is not live is skipped)
+    if (lvl == 0) on = on && (flags[v] & F_UP) && (flags[d] & F_UP);
+    uint32_t an = 0, en = 0, kn = 0;
+    if (on) R.counts(v, an, en, kn);
+    uint32_t emit = 0, ft = 0;
+    uint32_t child[LN == 1 ? RL_ROW : 1];
+    if constexpr (LN == RL_ROW) {
+        // entry g of each row in lane g
+        const uint32_t e = g < en ? R.com[(size_t)v * RL_ROW + g] : PSIM_NONE;
+        const uint32_t a = g < an ? R.act[(size_t)v * RL_ROW + g] : PSIM_NONE;
+        const uint32_t k = g < kn ? R.conn[(size_t)v * RL_ROW + g] : PSIM_NONE;
+        const uint32_t p = e & ~PSIM_MAP_BIT;
+        bool in_act = false, dn = false, pl = false, d_act = false, d_dn = false, d_pl = false;
+#pragma unroll
+        for (uint32_t q = 0; q < RL_ROW; q++) {        // (every lane of the wave: no branch around a shuffle)
+            const uint32_t aq = shfl(a, (int)(gb + q)), kq = shfl(k, (int)(gb + q));
+            in_act |= aq == p; dn |= kq == (p | PSIM_CONN_DOWN); pl |= kq == p;
+            d_act |= aq == d; d_dn |= kq == (d | PSIM_CONN_DOWN); d_pl |= kq == d;
+        }
+        const bool d_conn = rl_state(v != d, d_act, d_dn, d_pl) == RL_CONN;      // (d is live: the case is)
+        bool fwd = false;
+        if (on && g == 0) fwd = rl_decide(sh, tl, j, tt, T, c, lvl, d_act, d_conn, ft);
+        fwd = shfl(fwd ? 1u : 0u, (int)gb) != 0; ft = shfl(ft, (int)gb);
+        const bool oe = fwd && g < en && e != v;
+        const bool usable = oe && rl_state(rl_live(flags, N, v, p), in_act, dn, pl) == RL_CONN;
+        const uint32_t nrel = popc((ballot(usable) >> gb) & 0xFFull), nref = popc((ballot(oe && !usable) >> gb) & 0xFFull);
+        if (g == 0 && nrel) atomicAdd(&sh[RF_RELAY * PSIM_RELAY_CASES + j], c * nrel);
+        if (g == 0 && nref) atomicAdd(&sh[RF_REFUSED * PSIM_RELAY_CASES + j], c * nref);
+        if (usable) { emit = 1; child[0] = p; }
+    } else {
+        if (on) {
+            uint32_t e[RL_ROW], a[RL_ROW], k[RL_ROW];
+            const uint4* re = reinterpret_cast<const uint4*>(R.com + (size_t)v * RL_ROW);
+            const uint4* ra = reinterpret_cast<const uint4*>(R.act + (size_t)v * RL_ROW);
+            const uint4* rk = reinterpret_cast<const uint4*>(R.conn + (size_t)v * RL_ROW);
+            const uint4 e0 = re[0], e1 = re[1], a0 = ra[0], a1 = ra[1], k0 = rk[0], k1 = rk[1];
+            e[0] = e0.x; e[1] = e0.y; e[2] = e0.z; e[3] = e0.w; e[4] = e1.x; e[5] = e1.y; e[6] = e1.z; e[7] = e1.w;
+            a[0] = a0.x; a[1] = a0.y; a[2] = a0.z; a[3] = a0.w; a[4] = a1.x; a[5] = a1.y; a[6] = a1.z; a[7] = a1.w;
+            k[0] = k0.x; k[1] = k0.y; k[2] = k0.z; k[3] = k0.w; k[4] = k1.x; k[5] = k1.y; k[6] = k1.z; k[7] = k1.w;
+#pragma unroll
+            for (uint32_t q = 0; q < RL_ROW; q++) {
+                if (q >= an) a[q] = PSIM_NONE;
+                if (q >= kn) k[q] = PSIM_NONE;
+            }
+            bool d_act = false, d_dn = false, d_pl = false;
+#pragma unroll
+            for (uint32_t q = 0; q < RL_ROW; q++) { d_act |= a[q] == d; d_dn |= k[q] == (d | PSIM_CONN_DOWN); d_pl |= k[q] == d; }
+            const bool d_conn = rl_state(v != d, d_act, d_dn, d_pl) == RL_CONN;
+            if (rl_decide(sh, tl, j, tt, T, c, lvl, d_act, d_conn, ft)) {
+                uint32_t nref = 0;
+#pragma unroll
+                for (uint32_t r = 0; r < RL_ROW; r++) {
+                    if (r >= en || e[r] == v) continue;
+                    const uint32_t p = e[r] & ~PSIM_MAP_BIT;
+                    bool in_act = false, dn = false, pl = false;
+#pragma unroll
+                    for (uint32_t q = 0; q < RL_ROW; q++) { in_act |= a[q] == p; dn |= k[q] == (p | PSIM_CONN_DOWN); pl |= k[q] == p; }
+                    if (rl_state(rl_live(flags, N, v, p), in_act, dn, pl) == RL_CONN) child[emit++] = p;
+                    else nref++;
+                }
+                if (emit) atomicAdd(&sh[RF_RELAY * PSIM_RELAY_CASES + j], c * emit);
+                if (nref) atomicAdd(&sh[RF_REFUSED * PSIM_RELAY_CASES + j], c * nref);
+            }
+        }
+    }
+    // the block's children side by side: one returning global add a block
+    uint32_t tot;
+    const uint32_t at = block_excl<uint32_t>(emit, &tot);
+    if (threadIdx.x == 0) sh_base = tot ? atomicAdd(&rv[RV_CHILD], (unsigned long long)tot) : 0ull;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < (LN == 1 ? RL_ROW : 1); r++)
+        if (r < emit) { ckey[sh_base + at + r] = rl_key(j, ft - 1, child[r]); ccnt[sh_base + at + r] = c; }
+    for (uint32_t q = threadIdx.x; q < RF_FIELDS * PSIM_RELAY_CASES; q += blockDim.x) {
+        if (q / PSIM_RELAY_CASES == RF_FIRST) { if (sh[q] != RL_EMPTY) atomicMin(&tl[q], sh[q]); }
+        else if (sh[q]) atomicAdd(&tl[q], sh[q]);
+    }
+}
+
+// tkey: RL_EMPTY in every free slot; mask: the slots - 1 (a power of two, at
+// least twice the children, so a probe ends at a free slot)
+__global__ void __launch_bounds__(BLK) k_rl_merge(const unsigned long long* __restrict__ ckey,
+                                                  const unsigned long long* __restrict__ ccnt, uint64_t m,
+                                                  unsigned long long* tkey, unsigned long long* tcnt, uint64_t mask) {
+    const uint64_t t = (uint64_t)blockIdx.x * BLK + threadIdx.x;
+    if (t >= m) return;
+    const unsigned long long key = ckey[t], c = ccnt[t];
+    uint64_t s = mix64(key) & mask;
+    for (uint64_t it = 0; it <= mask; it++, s = (s + 1) & mask) {
+        // (a slot goes from free to one key once: a key read here is final, a free slot is tried)
+        unsigned long long old = __hip_atomic_load(&tkey[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == RL_EMPTY) old = atomicCAS(&tkey[s], RL_EMPTY, key);
+        if (old == RL_EMPTY || old == key) { atomicAdd(&tcnt[s], c); return; }
+    }
+}
+
+__global__ void __launch_bounds__(BLK) k_rl_compact(const unsigned long long* __restrict__ tkey,
+                                                    const unsigned long long* __restrict__ tcnt, uint64_t slots,
+                                                    unsigned long long* fkey, unsigned long long* fcnt,
+                                                    unsigned long long* rv) {
+    __shared__ unsigned long long sh[2 * PSIM_RELAY_CASES];
+    __shared__ unsigned long long sh_base;
+    if (threadIdx.x < 2 * PSIM_RELAY_CASES) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t s = (uint64_t)blockIdx.x * BLK + threadIdx.x;
+    const unsigned long long key = s < slots ? tkey[s] : RL_EMPTY;
+    const bool used = key != RL_EMPTY;
+    const unsigned long long c = used ? tcnt[s] : 0ull;
+    if (used) {
+        atomicAdd(&sh[key >> 32], 1ull);
+        atomicAdd(&sh[PSIM_RELAY_CASES + (key >> 32)], c);
+    }
+    uint32_t tot;
+    const uint32_t at = block_excl<uint32_t>(used ? 1u : 0u, &tot);
+    if (threadIdx.x == 0) sh_base = tot ? atomicAdd(&rv[RV_NEXT], (unsigned long long)tot) : 0ull;
+    __syncthreads();
+    if (used) { fkey[sh_base + at] = key; fcnt[sh_base + at] = c; }
+    if (threadIdx.x < 2 * PSIM_RELAY_CASES && sh[threadIdx.x]) atomicAdd(&rv[RV_DISTINCT + threadIdx.x], sh[threadIdx.x]);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- host --
@@ -1863,5 +2145,147 @@ extern "C" int psim_get_tree_metrics(psim_handle* h, uint32_t root, uint32_t max
     out->links_from_reached = fv[TF_LFR]; out->overlay_reached = fv[TF_OREACH]; out->both_reached = fv[TF_BOTH];
     out->depth_sum_both = fv[TF_DSUM]; out->dist_sum_both = fv[TF_LSUM];
     out->deeper = fv[TF_DEEPER]; out->shallower = fv[TF_SHALLOWER];
+    return PSIM_OK;
+}
+
+// PSIM_RELAY_LANES=8: an 8-lane group an entry in k_rl_expand, for A/B
+// (DESIGN.md "Transitive unicast": 2.4 times the kernel time of the default);
+// anything else: a lane an entry
+static uint32_t rl_lanes() {
+    const char* e = getenv("PSIM_RELAY_LANES");
+    return e && atoi(e) == (int)RL_ROW ? RL_ROW : 1u;
+}
+// the merge table's first size, a power of two (PSIM_RELAY_SLOTS, a test
+// hook: a small one makes a small run wrap its probes and regrow)
+static uint64_t rl_slots() {
+    const char* e = getenv("PSIM_RELAY_SLOTS");
+    const uint64_t want = e ? strtoull(e, nullptr, 10) : 0;
+    uint64_t s = 16;
+    while (s < (want ? std::min<uint64_t>(want, 1ull << 30) : 1ull << 16)) s <<= 1;
+    return s;
+}
+
+// The rows k_rl_census and k_rl_expand read: one shard's in place; virtual
+// shards and ranks gather them by global id as gather_active_rows does (100 B
+// a node), and every process then runs the same kernels over the whole overlay
+struct RlGather { TmpBuf<uint32_t> act, com, conn, cnt; };
+static int rl_rows(psim_handle* h, hipStream_t st, RlGather& b, RlRows& R) {
+    if (!h->ranked && h->shards.size() == 1) {
+        Shard* s = h->shards[0];
+        R = RlRows{s->hdr.p, nullptr, s->act.p, s->pt_com.p, s->conn.p};
+        return PSIM_OK;
+    }
+    const uint32_t per = h->per;
+    const size_t npad = (size_t)per * h->G;
+    TRY(b.act.alloc_on(npad * RL_ROW, st)); TRY(b.com.alloc_on(npad * RL_ROW, st));
+    TRY(b.conn.alloc_on(npad * RL_ROW, st)); TRY(b.cnt.alloc_on(npad, st));
+    for (Shard* s : h->shards)
+        if (s->n)
+            k_rl_pack<<<grid_for(s->n), BLK, 0, st>>>(s->hdr.p, s->act.p, s->pt_com.p, s->conn.p, s->n,
+                                                      b.act.p + (size_t)s->lo * RL_ROW, b.com.p + (size_t)s->lo * RL_ROW,
+                                                      b.conn.p + (size_t)s->lo * RL_ROW, b.cnt.p + s->lo);
+    HIP_TRY(hipGetLastError());
+    if (h->ranked) {
+        const size_t off = (size_t)h->rank * per;
+        TRY(h->comm->all_gather(b.act.p + off * RL_ROW, b.act.p, (size_t)per * RL_ROW * 4, st));
+        TRY(h->comm->all_gather(b.com.p + off * RL_ROW, b.com.p, (size_t)per * RL_ROW * 4, st));
+        TRY(h->comm->all_gather(b.conn.p + off * RL_ROW, b.conn.p, (size_t)per * RL_ROW * 4, st));
+        TRY(h->comm->all_gather(b.cnt.p + off, b.cnt.p, (size_t)per * 4, st));
+    }
+    R = RlRows{nullptr, b.cnt.p, b.act.p, b.com.p, b.conn.p};
+    return PSIM_OK;
+}
+
+extern "C" int psim_get_relay_reach(psim_handle* h, const psim_relay_case* cases, size_t n_cases, uint32_t max_levels,
+                                    psim_relay_reach* out) {
+    if (!h || !out || (n_cases && !cases) || n_cases > PSIM_RELAY_CASES) return PSIM_EINVAL;
+    const uint32_t nc = (uint32_t)n_cases;
+    for (uint32_t j = 0; j < nc; j++)
+        if (cases[j].reserved || !cases[j].ttl || cases[j].ttl > PSIM_RELAY_MAX_TTL || cases[j].source == cases[j].target)
+            return PSIM_EINVAL;
+    if (h->cfg.manager != PSIM_MANAGER_HYPARVIEW || h->hosted || !h->cfg.plumtree)
+        return PSIM_EUNSUPPORTED;                // (hosted: a collective)
+    if (h->round_open) return PSIM_ESTATE;
+    const uint32_t N = h->N;
+    for (uint32_t j = 0; j < nc; j++)
+        if (cases[j].source >= N || cases[j].target >= N) return PSIM_ERANGE;
+    hipStream_t st; const uint8_t* fl;
+    TRY(getter_begin(h, out, sizeof *out, st, fl));
+    // 1. the rows, and the census over them
+    RlGather gb;
+    RlRows R;
+    TmpBuf<unsigned long long> cs, tl, rv;
+    TRY(rl_rows(h, st, gb, R));
+    TRY(cs.alloc_on(RC_N, st));
+    k_rl_census<<<grid_for((uint64_t)N * 16), BLK, 0, st>>>(R, fl, N, cs.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long cv[RC_N];
+    TRY(read_back(st, cv, cs.p, RC_N));
+    out->n_up = cv[RC_NUP]; out->out_entries = cv[RC_ENT]; out->out_usable = cv[RC_USE];
+    out->out_nonmember = cv[RC_NONMEM]; out->members_down = cv[RC_DOWN];
+    for (int k = 0; k < PSIM_HIST_BINS; k++) out->out_degree[k] = cv[RC_DEG + k];
+    if (!nc) return PSIM_OK;
+    // 2. the flood, a level at a time: expand, merge by key, compact
+    const uint32_t cap = !max_levels || max_levels > PSIM_RELAY_MAX_TTL ? PSIM_RELAY_MAX_TTL : max_levels;
+    const uint32_t lanes = rl_lanes();
+    const auto expand = lanes == 1 ? k_rl_expand<1> : k_rl_expand<RL_ROW>;
+    TmpBuf<unsigned long long> fkey, fcnt, ckey, ccnt, tkey, tcnt;
+    TmpBuf<uint32_t> dpar;
+    uint32_t par[RP_N] = {0};
+    unsigned long long k0[PSIM_RELAY_CASES], c0[PSIM_RELAY_CASES];
+    for (uint32_t j = 0; j < nc; j++) {
+        par[RP_DST + j] = cases[j].target; par[RP_TTL + j] = cases[j].ttl;
+        k0[j] = ((unsigned long long)j << 32) | ((unsigned long long)cases[j].ttl << KEY_DST_BITS) | cases[j].source;
+        c0[j] = 1;
+    }
+    TRY(tl.alloc_on(RF_N, st)); TRY(rv.alloc_on(RV_N, st)); TRY(dpar.alloc_on(RP_N, st));
+    TRY(fkey.ensure(nc)); TRY(fcnt.ensure(nc));
+    HIP_TRY(hipMemsetAsync(tl.p + RF_FIRST * PSIM_RELAY_CASES, 0xFF, PSIM_RELAY_CASES * 8, st));
+    HIP_TRY(hipMemcpyAsync(dpar.p, par, sizeof par, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(fkey.p, k0, nc * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(fcnt.p, c0, nc * 8, hipMemcpyHostToDevice, st));
+    uint64_t nf = nc, slots = rl_slots();
+    for (uint32_t lvl = 0; nf && lvl <= cap; lvl++) {
+        if (nf > (1ull << 31)) return PSIM_ENOMEM;   // (the children of more entries: past any device's memory)
+        TRY(ckey.ensure(nf * RL_ROW)); TRY(ccnt.ensure(nf * RL_ROW));
+        HIP_TRY(hipMemsetAsync(rv.p, 0, RV_N * 8, st));
+        expand<<<grid_for(nf * lanes), BLK, 0, st>>>(R, fl, N, dpar.p, fkey.p, fcnt.p, nf, lvl, ckey.p, ccnt.p, rv.p, tl.p);
+        HIP_TRY(hipGetLastError());
+        unsigned long long m = 0;
+        TRY(read_back(st, &m, rv.p + RV_CHILD));
+        if (!m) break;
+        while (slots < 2 * m) slots <<= 1;
+        TRY(tkey.ensure(slots)); TRY(tcnt.ensure(slots)); TRY(fkey.ensure(m)); TRY(fcnt.ensure(m));
+        HIP_TRY(hipMemsetAsync(tkey.p, 0xFF, slots * 8, st));
+        HIP_TRY(hipMemsetAsync(tcnt.p, 0, slots * 8, st));
+        k_rl_merge<<<grid_for(m), BLK, 0, st>>>(ckey.p, ccnt.p, m, tkey.p, tcnt.p, slots - 1);
+        k_rl_compact<<<grid_for(slots), BLK, 0, st>>>(tkey.p, tcnt.p, slots, fkey.p, fcnt.p, rv.p);
+        HIP_TRY(hipGetLastError());
+        unsigned long long lv[RV_N];
+        TRY(read_back(st, lv, rv.p, RV_N));
+        nf = lv[RV_NEXT];
+        for (uint32_t j = 0; j < PSIM_RELAY_CASES; j++) {
+            if (!lv[RV_DISTINCT + j]) continue;
+            if (lvl + 1 <= cap) {
+                out->levels[j] = lvl + 1;
+                out->peak[j] = std::max<uint64_t>(out->peak[j], lv[RV_DISTINCT + j]);
+                out->levels_max = std::max<uint64_t>(out->levels_max, lvl + 1);
+            } else {
+                out->truncated_mask |= 1ull << j;
+                out->in_flight[j] = lv[RV_SUM + j];
+            }
+        }
+    }
+    unsigned long long tv[RF_N];
+    TRY(read_back(st, tv, tl.p, RF_N));
+    out->live_mask = tv[RF_LIVE]; out->direct_mask = tv[RF_DIRECT];
+    out->cases_live = (uint64_t)__builtin_popcountll(tv[RF_LIVE]);
+    for (uint32_t j = 0; j < PSIM_RELAY_CASES; j++) {
+        out->delivered[j] = tv[RF_DELIV * PSIM_RELAY_CASES + j]; out->hop_sum[j] = tv[RF_HOPS * PSIM_RELAY_CASES + j];
+        out->relays[j] = tv[RF_RELAY * PSIM_RELAY_CASES + j]; out->refused[j] = tv[RF_REFUSED * PSIM_RELAY_CASES + j];
+        out->expired[j] = tv[RF_EXPIRED * PSIM_RELAY_CASES + j]; out->restarts[j] = tv[RF_RESTART * PSIM_RELAY_CASES + j];
+        const unsigned long long f = tv[RF_FIRST * PSIM_RELAY_CASES + j];
+        out->first_hop[j] = f == RL_EMPTY ? 0 : f;
+    }
     return PSIM_OK;
 }

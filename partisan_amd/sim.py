@@ -501,6 +501,33 @@ class Simulator(_Driver):
             out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
         return out
 
+    def relay_reach(self, sources, targets, ttls, max_levels=0):
+        """Up to 64 transitive unicasts over the frozen overlay
+        (psim_relay_reach) as a dict of ints / arrays; a collective on rank
+        handles.  Case j sends from sources[j] to targets[j] with
+        {broadcast, true} and {transitive, true}: directly where the source
+        holds a connection, else as the relay_message flood with ttl ttls[j]
+        (a scalar: the same for every case).  max_levels caps the levels run
+        (0: 16)."""
+        src = np.ascontiguousarray(sources, np.uint32).reshape(-1)
+        dst = np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        ttl = np.full(src.size, ttls, np.uint32) if np.ndim(ttls) == 0 else np.ascontiguousarray(ttls, np.uint32).reshape(-1)
+        if not src.size == dst.size == ttl.size:
+            raise ValueError("sources, targets and ttls differ in length")
+        cases = (_abi.PsimRelayCase * max(src.size, 1))()
+        for j in range(src.size):
+            cases[j].source, cases[j].target, cases[j].ttl = int(src[j]), int(dst[j]), int(ttl[j])
+        m = _abi.PsimRelayReach()
+        self._check(self._extra["get_relay_reach"](self._h, cases if src.size else None, src.size, max_levels,
+                                                   C.byref(m)), "get_relay_reach")
+        out = {}
+        for name, _ in _abi.PsimRelayReach._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(m, name)
+            out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
+        return out
+
     # ---- the message trace (psim_trace_watch / psim_trace_read / psim_trace_clear)
     def trace_watch(self, nodes=None, to=True, frm=True, types=None, capacity=1 << 20):
         """Arm a watch: from the next round on, the records sent to (`to`) or
