@@ -452,6 +452,66 @@ typedef struct psim_tree_metrics {
     uint64_t reserved[8];
 } psim_tree_metrics;
 
+/* Latency-weighted paths over the overlay, computed on the device (DESIGN.md
+ * "Latency-weighted paths").  The weight of a link (i, p) is
+ * w(i, p) = psim_xbot_latency(cfg.seed, i, p), whatever the manager: 0 ..
+ * 1024.  L is the link set psim_graph_metrics counts (i live, p != i, p live,
+ * repeats dropped).  Everything is an integer, so the struct is bit-exact
+ * whatever the order of any sum.
+ *   Cheapest paths: D_r(s, v) is the least total weight of a path s -> v over
+ *     L with at most r links (no such path: infinite).  Sweep r turns D_(r-1)
+ *     into D_r; the call reports D_R, R the first r at which no distance of
+ *     any slot fell, or the sweep cap if that comes first.  Slot j =
+ *     sources[j]; a dead source's slot stays zero.  "Fell" is strictly lower:
+ *     a link of weight 0 (two nodes in one torus cell) keeps no sweep alive.
+ *   The tree half, with tree_root = R != PSIM_NONE: T is psim_tree_metrics'
+ *     eager link set of R; the same computation with the one source R, once
+ *     over T (the tree latency of v) and once over L (its overlay latency),
+ *     under the same sweep cap.  With R not live every field from tree_links
+ *     on is zero. */
+#define PSIM_LAT_SOURCES 64
+typedef struct psim_latency_metrics {
+    uint64_t n_up;                           /* live nodes */
+    uint64_t links;                          /* |L| */
+    uint64_t link_cost_sum;                  /* sum of w over L */
+    uint64_t link_cost[PSIM_HIST_BINS];      /* links by w >> 4, the last bin = 1008 or more (w = 1024 included) */
+    uint64_t link_nodes;                     /* live nodes with k_i >= 1 */
+    uint64_t worst_sum;                      /* over those: the sum of the largest w of their row (what X-BOT's
+                                                select_worst_in_active_view looks at) */
+    uint64_t best_sum;                       /* ... of the smallest */
+    uint64_t sources_live;                   /* live nodes among the sources */
+    uint64_t live_mask;                      /* bit j: sources[j] is live */
+    uint64_t reach[PSIM_LAT_SOURCES];        /* per slot: the nodes v != sources[j] with finite D_R */
+    uint64_t lat_sum[PSIM_LAT_SOURCES];      /* per slot: the sum of those D_R */
+    uint64_t lat_ecc[PSIM_LAT_SOURCES];      /* per slot: the largest of them */
+    uint64_t last_sweep[PSIM_LAT_SOURCES];   /* per slot: the last sweep that lowered a distance of the slot */
+    uint64_t lat[PSIM_HIST_BINS];            /* pairs (slot j, v) with finite D_R by D_R >> 8, the last bin =
+                                                16128 or more */
+    uint64_t lat_sum_all;                    /* the exact sum of those D_R (not saturated) */
+    uint64_t lat_max;                        /* the largest */
+    uint64_t pairs_reached;                  /* their number */
+    uint64_t pairs_unreached;                /* sources_live (n_up - 1) - pairs_reached */
+    uint64_t sweeps;                         /* R: sweeps run (the last one may have lowered nothing) */
+    uint64_t truncated_mask;                 /* bit j: the sweep cap ended slot j with sweep `cap` still lowering a
+                                                distance; its figures are those of D_cap */
+    uint64_t tree_root_live;                 /* 1: tree_root was given and is live */
+    uint64_t tree_links;                     /* |T| */
+    uint64_t tree_link_cost_sum;             /* sum of w over T */
+    uint64_t tree_reached;                   /* over T: nodes v != R with finite tree latency */
+    uint64_t tree_lat_sum;                   /* the sum of those latencies */
+    uint64_t tree_lat_max;                   /* the largest */
+    uint64_t tree_sweeps;                    /* sweeps the pass over T ran (as `sweeps`) */
+    uint64_t overlay_reached;                /* over L: nodes v != R with finite overlay latency */
+    uint64_t both_reached;                   /* v != R finite in both */
+    uint64_t tree_lat_sum_both;              /* over those: tree latencies */
+    uint64_t overlay_lat_sum_both;           /* ... overlay latencies (the ratio: the tree's latency stretch) */
+    uint64_t slower;                         /* ... whose tree latency exceeds the overlay latency */
+    uint64_t faster;                         /* ... the opposite (eager links to non-members exist) */
+    uint64_t tree_truncated;                 /* 1: the sweep cap ended either pass with sweep `cap` still lowering
+                                                a distance */
+    uint64_t reserved[8];
+} psim_latency_metrics;
+
 /* Broadcast reach under mass node failure, computed on the device (DESIGN.md
  * "Reach under mass failure"): up to PSIM_FAIL_CASES failure cases in one
  * bit-parallel BFS, bit j of a node's word = "in case j this node survived
@@ -853,6 +913,25 @@ int psim_get_gossip_reach(psim_handle *h, const psim_gossip_case *cases, size_t 
  * (INTEGRATION.md). */
 int psim_get_relay_reach(psim_handle *h, const psim_relay_case *cases, size_t n_cases, uint32_t max_levels,
                          psim_relay_reach *out);
+/* Link costs and cheapest paths by latency from up to PSIM_LAT_SOURCES
+ * sources (psim_latency_metrics above), on the device, for HyParView, X-BOT
+ * and SCAMP v1 / v2 handles of any shard count.  n_sources == 0 with
+ * tree_root == PSIM_NONE fills the link census only.  tree_root != PSIM_NONE
+ * adds the tree half (HyParView and X-BOT handles with cfg.plumtree set).
+ * max_sweeps caps the sweeps of every pass: 0 means PSIM_GRAPH_MAX_LEVELS, and
+ * larger values are clamped to it.  Errors, in this order: PSIM_EINVAL for a
+ * null h or out, null sources with n_sources > 0 or n_sources >
+ * PSIM_LAT_SOURCES; PSIM_EUNSUPPORTED for full-membership and host-exchange
+ * handles, and for a tree_root on a pluggable handle or with plumtree = 0;
+ * PSIM_ESTATE with a round open; PSIM_ERANGE for a source or a tree_root
+ * >= n_nodes (a dead one is legal and skipped); PSIM_EINVAL for a repeated
+ * source; PSIM_ENOMEM if the temporaries (two rows of 64 distances a node,
+ * 512 B) cannot be had: the handle stays usable.  Read-only: the rounds
+ * stepped after it are those of a run without it.  A collective on rank
+ * handles (every rank calls with the same arguments; every rank gets the same
+ * struct).  No Erlang binding yet. */
+int psim_get_latency_metrics(psim_handle *h, const uint32_t *sources, size_t n_sources, uint32_t tree_root,
+                             uint32_t max_sweeps, psim_latency_metrics *out);
 /* Snapshot of the whole simulation state of this process (node rows,
  * in-flight messages, round, events not yet applied are not included):
  * with buf == NULL (or cap too small) only *need is set.  psim_restore

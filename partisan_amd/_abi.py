@@ -175,6 +175,30 @@ class PsimTreeMetrics(C.Structure):
     ]
 
 
+LAT_SOURCES = 64
+
+
+class PsimLatencyMetrics(C.Structure):
+    _fields_ = [
+        ("n_up", C.c_uint64), ("links", C.c_uint64), ("link_cost_sum", C.c_uint64),
+        ("link_cost", C.c_uint64 * HIST_BINS),
+        ("link_nodes", C.c_uint64), ("worst_sum", C.c_uint64), ("best_sum", C.c_uint64),
+        ("sources_live", C.c_uint64), ("live_mask", C.c_uint64),
+        ("reach", C.c_uint64 * LAT_SOURCES), ("lat_sum", C.c_uint64 * LAT_SOURCES),
+        ("lat_ecc", C.c_uint64 * LAT_SOURCES), ("last_sweep", C.c_uint64 * LAT_SOURCES),
+        ("lat", C.c_uint64 * HIST_BINS), ("lat_sum_all", C.c_uint64), ("lat_max", C.c_uint64),
+        ("pairs_reached", C.c_uint64), ("pairs_unreached", C.c_uint64),
+        ("sweeps", C.c_uint64), ("truncated_mask", C.c_uint64),
+        ("tree_root_live", C.c_uint64), ("tree_links", C.c_uint64), ("tree_link_cost_sum", C.c_uint64),
+        ("tree_reached", C.c_uint64), ("tree_lat_sum", C.c_uint64), ("tree_lat_max", C.c_uint64),
+        ("tree_sweeps", C.c_uint64),
+        ("overlay_reached", C.c_uint64), ("both_reached", C.c_uint64),
+        ("tree_lat_sum_both", C.c_uint64), ("overlay_lat_sum_both", C.c_uint64),
+        ("slower", C.c_uint64), ("faster", C.c_uint64), ("tree_truncated", C.c_uint64),
+        ("reserved", C.c_uint64 * 8),
+    ]
+
+
 FAIL_CASES = 64
 
 
@@ -288,6 +312,8 @@ GPU_ONLY = {
     "get_gossip_reach": (C.c_int, [_H, C.POINTER(PsimGossipCase), C.c_size_t, C.c_uint64, C.c_uint32,
                                    C.POINTER(PsimGossipReach)]),
     "get_relay_reach": (C.c_int, [_H, C.POINTER(PsimRelayCase), C.c_size_t, C.c_uint32, C.POINTER(PsimRelayReach)]),
+    "get_latency_metrics": (C.c_int, [_H, _P32, C.c_size_t, C.c_uint32, C.c_uint32,
+                                      C.POINTER(PsimLatencyMetrics)]),
     # the message trace (no oracle twin: the tests filter Oracle.inbox())
     "trace_watch": (C.c_int, [_H, _P32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_size_t]),
     "trace_read": (C.c_int, [_H, _P32, _P32, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),

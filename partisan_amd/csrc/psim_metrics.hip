@@ -1,4 +1,4 @@
-// psim_metrics.hip -- the read-only analyses of the overlay behind seven
+// psim_metrics.hip -- the read-only analyses of the overlay behind eight
 // getters of include/partisan_gpu_sim.h; no round runs any of it:
 //   psim_get_histograms           HyParView's views, the tracked broadcast, components
 //   psim_get_strategy_histograms  the pluggable strategies' views (SCAMP's as a CSR)
@@ -7,10 +7,12 @@
 //   psim_get_gossip_reach         ... pushed over at most `fanout` links a node
 //   psim_get_tree_metrics         a Plumtree root's eager tree against the overlay
 //   psim_get_relay_reach          the transitive unicast's relay flood, 64 cases
+//   psim_get_latency_metrics      link costs, cheapest paths by latency from 64 sources
 // Each waits for every shard's stream, works on the first shard's, and is a
 // collective on ranks.  Shared by the analyses: Links (a link set as rows) and
-// link_set (its host side), bfs_levels (the word BFS's level loop), wave_or /
-// tile_add (per-bit counts of a wave's words), getter_begin, level_cap.
+// link_set (its host side), tree_set (a root's eager links), bfs_levels (the
+// word BFS's level loop), wave_or / tile_add (per-bit counts of a wave's
+// words), getter_begin, level_cap.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1477,6 +1479,267 @@ __global__ void __launch_bounds__(BLK) k_rl_compact(const unsigned long long* __
     if (threadIdx.x < 2 * PSIM_RELAY_CASES && sh[threadIdx.x]) atomicAdd(&rv[RV_DISTINCT + threadIdx.x], sh[threadIdx.x]);
 }
 
+// ---------------------------------------------- latency-weighted paths --
+// psim_get_latency_metrics (psim_latency_metrics in the header defines every
+// field).  A node's state is a row of LT_W distances, lane = source slot,
+// 256 B: a wave reads or relaxes a whole row in one coalesced access.  Two rows
+// a node: `cur` takes the atomicMins of a sweep, `prev` is the row as of the
+// end of the sweep before, and the only thing a push reads -- so sweep r
+// computes exactly D_r whatever the order of the atomics.  The frontier words
+// are WordBfs' shape: bit j of front[i] = "slot j of node i fell last sweep".
+//   k_lt_cell     a node's torus cell (20 bits), one mix64 a node (the A/B form of the weights)
+//   k_lt_census   a thread a node over its row of L (or T): the link costs
+//   k_lt_init     the rows' zeros at the live sources, their frontier bits
+//   k_lt_push     a wave takes 64 nodes' frontier words and relaxes the rows
+//                 of the nodes on the frontier, one after the other
+//   k_lt_push_list  a wave a node of the compacted frontier list
+//   k_lt_level    the fallen lanes cur -> prev, front = next, next = 0, the
+//                 frontier list, the sweep's OR word and node count
+//   k_lt_final    one pass over the rows: per slot reach, sum, max; the histogram
+//   k_lt_column / k_lt_tree   slot 0 of every row; the tree half's comparison
+constexpr uint32_t LT_W = PSIM_LAT_SOURCES;
+constexpr uint32_t LT_INF = 0xFFFFFFFFu;
+enum { LC_NUP = 0, LC_LINKS, LC_COST, LC_NODES, LC_WORST, LC_BEST, LC_HIST, LC_N = LC_HIST + PSIM_HIST_BINS };
+enum { LF_REACH = 0, LF_SUM = LT_W, LF_HIST = 2 * LT_W, LF_ECC = 2 * LT_W + PSIM_HIST_BINS, LF_N = LF_ECC + LT_W };
+enum { LR_TREACH = 0, LR_TSUM, LR_OREACH, LR_BOTH, LR_TSUMB, LR_OSUMB, LR_SLOWER, LR_FASTER, LR_TMAX, LR_N };
+
+DEV uint32_t lt_cell_of(uint64_t seed, uint32_t i) {
+    return (uint32_t)mix64(seed ^ ((uint64_t)i * 0x9E3779B97F4A7C15ull)) & 0xFFFFFu;
+}
+// w(i, p), i != p: from the cells (cell != nullptr), or xbot_latency itself
+DEV uint32_t lt_weight(const uint32_t* __restrict__ cell, uint64_t seed, uint32_t i, uint32_t p) {
+    if (!cell) return xbot_latency(seed, i, p);
+    const uint32_t a = cell[i], b = cell[p];
+    return xbot_axis(a & 1023u, b & 1023u) + xbot_axis(a >> 10, b >> 10);
+}
+
+__global__ void k_lt_cell(uint64_t seed, uint32_t n, uint32_t* cell) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) cell[i] = lt_cell_of(seed, i);
+}
+
+__global__ void __launch_bounds__(BLK) k_lt_census(Links ln, const uint8_t* __restrict__ flags, uint32_t n,
+                                                   const uint32_t* __restrict__ cell, uint64_t seed,
+                                                   unsigned long long* lc) {
+    __shared__ unsigned long long sh[LC_N];
+    for (uint32_t j = threadIdx.x; j < LC_N; j += blockDim.x) sh[j] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool up = i < n && (flags[i] & F_UP);
+    const uint32_t c = up ? ln.cnt[i] : 0;
+    uint32_t sum = 0, hi = 0, lo = LT_INF;
+    if (c) {
+        const uint32_t* row = ln.row(i);
+        for (uint32_t k = 0; k < c; k++) {
+            const uint32_t w = lt_weight(cell, seed, i, row[k]);
+            sum += w; hi = max(hi, w); lo = min(lo, w);
+            atomicAdd(&sh[LC_HIST + hbin(w >> 4)], 1ull);
+        }
+    }
+    const uint32_t nup = popc(ballot(up)), nodes = popc(ballot(c != 0));
+    const uint32_t links = sh_wave_sum(c), cost = sh_wave_sum(sum);          // (a wave: 64 * 128 * 1024 at the most)
+    const uint32_t worst = sh_wave_sum(hi), best = sh_wave_sum(c ? lo : 0u);
+    if (lane_id() == 0 && nup) {
+        atomicAdd(&sh[LC_NUP], (unsigned long long)nup);
+        if (nodes) {
+            atomicAdd(&sh[LC_LINKS], (unsigned long long)links); atomicAdd(&sh[LC_COST], (unsigned long long)cost);
+            atomicAdd(&sh[LC_NODES], (unsigned long long)nodes);
+            atomicAdd(&sh[LC_WORST], (unsigned long long)worst); atomicAdd(&sh[LC_BEST], (unsigned long long)best);
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < LC_N; j += blockDim.x)
+        if (sh[j]) atomicAdd(&lc[j], sh[j]);
+}
+
+// slot j starts at sources[j] if that node is live: distance 0 in both rows
+// (all others LT_INF), its frontier bit, its place in the frontier list; lv[0]:
+// the mask of such slots, lv[1]: their number (one block of 64 threads; the
+// sources are distinct and < n)
+__global__ void k_lt_init(const uint32_t* __restrict__ sources, uint32_t ns, const uint8_t* __restrict__ flags,
+                          uint32_t* cur, uint32_t* prev, unsigned long long* front, uint32_t* list,
+                          unsigned long long* lv) {
+    const uint32_t j = threadIdx.x;
+    const bool on = j < ns && (flags[sources[j]] & F_UP);
+    const uint64_t m = ballot(on);
+    if (on) {
+        const uint32_t s = sources[j];
+        cur[(size_t)s * LT_W + j] = 0; prev[(size_t)s * LT_W + j] = 0;
+        front[s] = 1ull << j;
+        list[popc(m & lt_mask())] = s;
+    }
+    if (j == 0) { lv[0] = m; lv[1] = popc(m); }
+}
+
+// the wave relaxes the out-links of frontier node i: lane j holds prev[i][j];
+// the row's ids and weights sit one link a lane (two for a long CSR row), so a
+// weight is computed once per link; per link the lanes of f do the atomicMin,
+// and the ballot of those that lowered the target is one atomicOr into next
+DEV void lt_relax(Links ln, const uint32_t* __restrict__ cell, uint64_t seed, uint32_t i, uint64_t f,
+                  const uint32_t* __restrict__ prev, uint32_t* cur, unsigned long long* next) {
+    const uint32_t l = lane_id();
+    const uint32_t c = min((uint32_t)ln.cnt[i], (uint32_t)PSIM_SVIEW_CAP);
+    if (!c) return;                                   // (uniform)
+    const uint32_t d = prev[(size_t)i * LT_W + l];
+    const bool mine = ((f >> l) & 1) && d != LT_INF;
+    uint32_t a, b, wa = 0, wb = 0;
+    sh_row_load(ln.row(i), c, a, b);
+    if (l < c) wa = lt_weight(cell, seed, i, a);
+    if (64 + l < c) wb = lt_weight(cell, seed, i, b);
+    for (uint32_t t = 0; t < c; t++) {                // (uniform)
+        const uint32_t p = t < 64 ? shfl(a, (int)t) : shfl(b, (int)(t - 64));
+        const uint32_t w = t < 64 ? shfl(wa, (int)t) : shfl(wb, (int)(t - 64));
+        const uint32_t nd = d + w;
+        uint32_t* at = cur + (size_t)p * LT_W + l;
+        // (a stale read can only be too large: a distance never rises)
+        const bool fell = mine && nd < *at && atomicMin(at, nd) > nd;
+        const uint64_t m = ballot(fell);
+        if (m && l == 0) atomicOr(&next[p], (unsigned long long)m);
+    }
+}
+
+__global__ void __launch_bounds__(BLK) k_lt_push(Links ln, uint32_t n, const uint32_t* __restrict__ cell,
+                                                 uint64_t seed, const unsigned long long* __restrict__ front,
+                                                 const uint32_t* __restrict__ prev, uint32_t* cur,
+                                                 unsigned long long* next) {
+    const uint32_t base = (blockIdx.x * (BLK / 64) + (threadIdx.x >> 6)) * 64;     // this wave's first node
+    const uint32_t mine = base + lane_id();
+    const uint64_t f = mine < n ? front[mine] : 0;
+    uint64_t todo = ballot(f != 0);
+    while (todo) {                                    // (uniform)
+        const int k = ffs64(todo);
+        todo &= todo - 1;
+        lt_relax(ln, cell, seed, base + (uint32_t)k, shfl64(f, k), prev, cur, next);
+    }
+}
+
+__global__ void __launch_bounds__(BLK) k_lt_push_list(Links ln, const uint32_t* __restrict__ list, uint32_t nf,
+                                                      const uint32_t* __restrict__ cell, uint64_t seed,
+                                                      const unsigned long long* __restrict__ front,
+                                                      const uint32_t* __restrict__ prev, uint32_t* cur,
+                                                      unsigned long long* next) {
+    const uint32_t q = blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);               // (uniform per wave)
+    if (q >= nf) return;
+    const uint32_t i = list[q];
+    lt_relax(ln, cell, seed, i, front[i], prev, cur, next);
+}
+
+// a wave takes 64 nodes: where next[i] != 0 its lanes of cur go to prev;
+// front = next, next = 0; the nodes go into the frontier list at lv[1]'s
+// count (list == nullptr: no list); lv[0]: the OR of the sweep's words
+__global__ void __launch_bounds__(BLK) k_lt_level(uint32_t n, unsigned long long* next, unsigned long long* front,
+                                                  const uint32_t* __restrict__ cur, uint32_t* prev, uint32_t* list,
+                                                  unsigned long long* lv) {
+    __shared__ unsigned long long sh_or;
+    if (threadIdx.x == 0) sh_or = 0;
+    __syncthreads();
+    const uint32_t l = lane_id();
+    const uint32_t base = (blockIdx.x * (BLK / 64) + (threadIdx.x >> 6)) * 64;
+    const uint32_t mine = base + l;
+    unsigned long long nx = 0;
+    if (mine < n) {
+        nx = next[mine];
+        if (nx) next[mine] = 0;
+        if (front[mine] != nx) front[mine] = nx;
+    }
+    const uint64_t some = ballot(nx != 0);
+    if (some) {                                       // (uniform)
+        uint64_t todo = some;
+        while (todo) {
+            const int k = ffs64(todo);
+            todo &= todo - 1;
+            const size_t at = (size_t)(base + (uint32_t)k) * LT_W + l;
+            if ((shfl64(nx, k) >> l) & 1) prev[at] = cur[at];
+        }
+        const uint64_t w = wave_or(nx);
+        uint32_t pos = 0;
+        if (l == 0) {
+            atomicOr(&sh_or, (unsigned long long)w);
+            pos = (uint32_t)atomicAdd(&lv[1], (unsigned long long)popc(some));
+        }
+        pos = shfl(pos, 0);
+        if (list && nx) list[pos + popc(some & lt_mask())] = mine;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && sh_or) atomicOr(&lv[0], sh_or);
+}
+
+// one pass over the rows after the last sweep: a wave a node at a time, lane =
+// slot; the per-slot counts stay in the lane's registers, then the block's LDS
+// tile, then one global add per block and word
+__global__ void __launch_bounds__(BLK) k_lt_final(const uint32_t* __restrict__ cur,
+                                                  const uint32_t* __restrict__ sources,
+                                                  const uint8_t* __restrict__ flags, uint32_t n, uint32_t per_wave,
+                                                  unsigned long long* lf) {
+    __shared__ unsigned long long sh[LF_N];
+    for (uint32_t j = threadIdx.x; j < LF_N; j += blockDim.x) sh[j] = 0;
+    __syncthreads();
+    const uint32_t l = lane_id();
+    const uint32_t src = sources[l];                  // (slots past the sources: never finite)
+    const uint32_t lo = (blockIdx.x * (BLK / 64) + (threadIdx.x >> 6)) * per_wave;
+    const uint32_t hi = min(n, lo + per_wave);
+    uint32_t reach = 0, ecc = 0;
+    unsigned long long sum = 0;
+    for (uint32_t v = lo; v < hi; v++) {              // (uniform)
+        if (!(flags[v] & F_UP)) continue;
+        const uint32_t d = cur[(size_t)v * LT_W + l];
+        if (d == LT_INF || v == src) continue;
+        reach++; sum += d; ecc = max(ecc, d);
+        atomicAdd(&sh[LF_HIST + hbin(d >> 8)], 1ull);
+    }
+    if (reach) {
+        atomicAdd(&sh[LF_REACH + l], (unsigned long long)reach);
+        atomicAdd(&sh[LF_SUM + l], sum);
+        atomicMax(&sh[LF_ECC + l], (unsigned long long)ecc);
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < LF_N; j += blockDim.x) {
+        if (!sh[j]) continue;
+        if (j >= LF_ECC) atomicMax(&lf[j], sh[j]);
+        else atomicAdd(&lf[j], sh[j]);
+    }
+}
+
+// slot 0 of every row
+__global__ void k_lt_column(const uint32_t* __restrict__ cur, uint32_t n, uint32_t* col) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) col[i] = cur[(size_t)i * LT_W];
+}
+
+// per live node v != root: its latency over T (dt) against that over L (dl)
+__global__ void __launch_bounds__(BLK) k_lt_tree(const uint32_t* __restrict__ dt, const uint32_t* __restrict__ dl,
+                                                 const uint8_t* __restrict__ flags, uint32_t n, uint32_t root,
+                                                 unsigned long long* lr) {
+    __shared__ unsigned long long sh[LR_N];
+    if (threadIdx.x < LR_N) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t s[LR_TMAX] = {0}, mx = 0;
+    if (i < n && i != root && (flags[i] & F_UP)) {
+        const uint32_t a = dt[i], b = dl[i];
+        if (a != LT_INF) { s[LR_TREACH] = 1; s[LR_TSUM] = a; mx = a; }
+        if (b != LT_INF) s[LR_OREACH] = 1;
+        if (a != LT_INF && b != LT_INF) {
+            s[LR_BOTH] = 1; s[LR_TSUMB] = a; s[LR_OSUMB] = b;
+            s[LR_SLOWER] = a > b ? 1u : 0u; s[LR_FASTER] = a < b ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < LR_TMAX; j++) {
+        const uint32_t v = sh_wave_sum(s[j]);         // (a wave's latencies: 64 * 2^22 at the most)
+        if (lane_id() == 0 && v) atomicAdd(&sh[j], (unsigned long long)v);
+    }
+    if (ballot(mx != 0)) {                            // (uniform)
+        for (int d = 32; d; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d));
+        if (lane_id() == 0) atomicMax(&sh[LR_TMAX], (unsigned long long)mx);
+    }
+    __syncthreads();
+    if (threadIdx.x < LR_N && sh[threadIdx.x]) {
+        if (threadIdx.x == LR_TMAX) atomicMax(&lr[threadIdx.x], sh[threadIdx.x]);
+        else atomicAdd(&lr[threadIdx.x], sh[threadIdx.x]);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- host --
@@ -2057,20 +2320,20 @@ static uint32_t tm_lanes() {
     return e && atoi(e) == 64 ? 64u : 16u;
 }
 
-extern "C" int psim_get_tree_metrics(psim_handle* h, uint32_t root, uint32_t max_levels, psim_tree_metrics* out) {
-    if (!h || !out) return PSIM_EINVAL;
-    if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE || h->hosted || !h->cfg.plumtree)
-        return PSIM_EUNSUPPORTED;                // (hosted: a collective)
-    if (h->round_open) return PSIM_ESTATE;
-    if (root >= h->N) return PSIM_ERANGE;
-    hipStream_t st; const uint8_t* fl;
-    TRY(getter_begin(h, out, sizeof *out, st, fl));
-    const uint32_t N = h->N, lanes = tm_lanes();
-    // 1. T as a CSR, the same on every rank, and the entry-level counts
+// A root's eager link set T (psim_tree_metrics defines it) as a CSR, the same
+// on every rank, with what its row pass counts: tm (TM_N words, summed over
+// ranks) and the in-degrees in T.  TreeSet owns the buffers
+struct TreeSet {
     ShCsr csr;
-    TmpBuf<unsigned long long> tm, tf, sym;
+    TmpBuf<unsigned long long> tm;
     TmpBuf<uint32_t> indeg;
-    TRY(tm.alloc_on(TM_N, st)); TRY(tf.alloc_on(TF_N, st)); TRY(sym.alloc_on(1, st)); TRY(indeg.alloc_on(N, st));
+};
+static int tree_set(psim_handle* h, hipStream_t st, const uint8_t* fl, uint32_t root, TreeSet& t) {
+    const uint32_t N = h->N, lanes = tm_lanes();
+    ShCsr& csr = t.csr;
+    TmpBuf<unsigned long long>& tm = t.tm;
+    TmpBuf<uint32_t>& indeg = t.indeg;
+    TRY(tm.alloc_on(TM_N, st)); TRY(indeg.alloc_on(N, st));
     TRY(csr_alloc(h, st, csr));
     const auto k_rows = lanes == 64 ? k_tm_rows<64> : k_tm_rows<16>;
     auto rows = [&](const uint32_t* off, uint32_t* adj) {
@@ -2092,6 +2355,26 @@ extern "C" int psim_get_tree_metrics(psim_handle* h, uint32_t root, uint32_t max
         TRY(h->comm->all_reduce(tm.p, TM_N, CType::U64, COp::SUM, st));
         TRY(h->comm->all_reduce(indeg.p, N, CType::U32, COp::SUM, st));
     }
+    return PSIM_OK;
+}
+
+extern "C" int psim_get_tree_metrics(psim_handle* h, uint32_t root, uint32_t max_levels, psim_tree_metrics* out) {
+    if (!h || !out) return PSIM_EINVAL;
+    if (h->cfg.manager == PSIM_MANAGER_PLUGGABLE || h->hosted || !h->cfg.plumtree)
+        return PSIM_EUNSUPPORTED;                // (hosted: a collective)
+    if (h->round_open) return PSIM_ESTATE;
+    if (root >= h->N) return PSIM_ERANGE;
+    hipStream_t st; const uint8_t* fl;
+    TRY(getter_begin(h, out, sizeof *out, st, fl));
+    const uint32_t N = h->N;
+    // 1. T as a CSR, the same on every rank, and the entry-level counts
+    TreeSet ts;
+    TmpBuf<unsigned long long> tf, sym;
+    TRY(tf.alloc_on(TF_N, st)); TRY(sym.alloc_on(1, st));
+    TRY(tree_set(h, st, fl, root, ts));
+    const ShCsr& csr = ts.csr;
+    const TmpBuf<unsigned long long>& tm = ts.tm;
+    const TmpBuf<uint32_t>& indeg = ts.indeg;
     const Links tree = csr.links();
     k_tm_sym<<<grid_for(N), BLK, 0, st>>>(tree, N, sym.p);
     HIP_TRY(hipGetLastError());
@@ -2287,5 +2570,182 @@ extern "C" int psim_get_relay_reach(psim_handle* h, const psim_relay_case* cases
         const unsigned long long f = tv[RF_FIRST * PSIM_RELAY_CASES + j];
         out->first_hop[j] = f == RL_EMPTY ? 0 : f;
     }
+    return PSIM_OK;
+}
+
+// PSIM_LAT_PUSH=list: k_lt_push_list over the compacted frontier, and
+// PSIM_LAT_CELL=cell: the cell array instead of xbot_latency per link, for A/B
+// (DESIGN.md "Latency-weighted paths": both measured slower); anything else:
+// the walk over all nodes, the weights per link
+static bool lt_env(const char* name, const char* value) {
+    const char* e = getenv(name);
+    return e && !strcmp(e, value);
+}
+
+// The rows and frontier words of the sweeps, allocated once a call and seeded
+// again for every pass
+struct LatRows {
+    TmpBuf<uint32_t> cur, prev, list, dsrc;
+    TmpBuf<unsigned long long> front, next, lv;
+    uint32_t cap = 0;
+    bool use_list = false;
+};
+static int lt_alloc(hipStream_t st, uint32_t N, uint32_t cap, LatRows& b) {
+    b.cap = cap;
+    b.use_list = lt_env("PSIM_LAT_PUSH", "list");
+    TRY(b.cur.ensure((size_t)N * LT_W, -1)); TRY(b.prev.ensure((size_t)N * LT_W, -1));
+    TRY(b.list.ensure(std::max<size_t>(N, LT_W), -1)); TRY(b.dsrc.ensure(LT_W, -1));
+    TRY(b.front.ensure(N, -1)); TRY(b.next.ensure(N, -1)); TRY(b.lv.ensure(2 * ((size_t)cap + 1), -1));
+    return PSIM_OK;
+}
+
+// The sweeps from the live nodes among src[0 .. ns) over `ln`: on return
+// b.cur holds D_R.  live: the mask of live slots; sweeps: R; trunc: the word
+// of sweep `cap` if that still lowered a distance; last[j] (nullptr: not
+// wanted): the last sweep that lowered one of slot j; front_sum: the frontier
+// nodes over all sweeps
+static int lt_run(hipStream_t st, Links ln, uint32_t N, const uint8_t* fl, const uint32_t* cell, uint64_t seed,
+                  LatRows& b, const uint32_t* src, uint32_t ns, uint64_t& live, uint64_t& sweeps, uint64_t& trunc,
+                  uint64_t* last) {
+    uint32_t s64[LT_W];
+    for (uint32_t j = 0; j < LT_W; j++) s64[j] = j < ns ? src[j] : PSIM_NONE;
+    live = sweeps = trunc = 0;
+    HIP_TRY(hipMemsetAsync(b.cur.p, 0xFF, (size_t)N * LT_W * 4, st));
+    HIP_TRY(hipMemsetAsync(b.prev.p, 0xFF, (size_t)N * LT_W * 4, st));
+    HIP_TRY(hipMemsetAsync(b.front.p, 0, (size_t)N * 8, st));
+    HIP_TRY(hipMemsetAsync(b.next.p, 0, (size_t)N * 8, st));
+    HIP_TRY(hipMemsetAsync(b.lv.p, 0, 2 * ((size_t)b.cap + 1) * 8, st));
+    HIP_TRY(hipMemcpyAsync(b.dsrc.p, s64, sizeof s64, hipMemcpyHostToDevice, st));
+    k_lt_init<<<1, 64, 0, st>>>(b.dsrc.p, ns, fl, b.cur.p, b.prev.p, b.front.p, b.list.p, b.lv.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long w[2] = {0, 0};
+    TRY(read_back(st, w, b.lv.p, 2));
+    live = w[0];
+    uint64_t nf = w[1];
+    if (!live) return PSIM_OK;
+    constexpr uint32_t WPB = BLK / 64;                // waves a block
+    for (uint32_t d = 1; d <= b.cap; d++) {
+        unsigned long long* lv = b.lv.p + 2 * (size_t)d;
+        if (b.use_list)
+            k_lt_push_list<<<(uint32_t)((nf + WPB - 1) / WPB), BLK, 0, st>>>(ln, b.list.p, (uint32_t)nf, cell, seed,
+                                                                             b.front.p, b.prev.p, b.cur.p, b.next.p);
+        else
+            k_lt_push<<<grid_for(N), BLK, 0, st>>>(ln, N, cell, seed, b.front.p, b.prev.p, b.cur.p, b.next.p);
+        k_lt_level<<<grid_for(N), BLK, 0, st>>>(N, b.next.p, b.front.p, b.cur.p, b.prev.p,
+                                                b.use_list ? b.list.p : nullptr, lv);
+        HIP_TRY(hipGetLastError());
+        TRY(read_back(st, w, lv, 2));
+        sweeps = d;
+        if (!w[0]) break;
+        nf = w[1];
+        if (last)
+            for (uint32_t j = 0; j < LT_W; j++)
+                if ((w[0] >> j) & 1) last[j] = d;
+        if (d == b.cap) trunc = w[0];
+    }
+    return PSIM_OK;
+}
+
+// the link costs of `ln` (L or T) into lc, LC_N words
+static int lt_census(hipStream_t st, Links ln, uint32_t N, const uint8_t* fl, const uint32_t* cell, uint64_t seed,
+                     unsigned long long* lc, unsigned long long* v) {
+    HIP_TRY(hipMemsetAsync(lc, 0, LC_N * 8, st));
+    k_lt_census<<<grid_for(N), BLK, 0, st>>>(ln, fl, N, cell, seed, lc);
+    HIP_TRY(hipGetLastError());
+    return read_back(st, v, lc, LC_N);
+}
+
+extern "C" int psim_get_latency_metrics(psim_handle* h, const uint32_t* sources, size_t n_sources, uint32_t tree_root,
+                                        uint32_t max_sweeps, psim_latency_metrics* out) {
+    static_assert(PSIM_LAT_SOURCES == 64, "a lane of a wave and a bit of a frontier word per source slot");
+    if (!h || !out || (n_sources && !sources) || n_sources > PSIM_LAT_SOURCES) return PSIM_EINVAL;
+    const bool pl = h->cfg.manager == PSIM_MANAGER_PLUGGABLE, tree = tree_root != PSIM_NONE;
+    if (h->hosted || (pl && h->cfg.strategy == PSIM_STRATEGY_FULL)) return PSIM_EUNSUPPORTED;   // (hosted: a collective)
+    if (tree && (pl || !h->cfg.plumtree)) return PSIM_EUNSUPPORTED;
+    if (h->round_open) return PSIM_ESTATE;
+    const uint32_t N = h->N, ns = (uint32_t)n_sources;
+    uint32_t src[PSIM_LAT_SOURCES] = {0};
+    for (uint32_t j = 0; j < ns; j++) {
+        if (sources[j] >= N) return PSIM_ERANGE;
+        src[j] = sources[j];
+    }
+    if (tree && tree_root >= N) return PSIM_ERANGE;
+    for (uint32_t j = 0; j < ns; j++)
+        for (uint32_t q = 0; q < j; q++)
+            if (src[q] == src[j]) return PSIM_EINVAL;
+    hipStream_t st; const uint8_t* fl;
+    TRY(getter_begin(h, out, sizeof *out, st, fl));
+    const uint64_t seed = h->cfg.seed;
+    // 1. L as rows, the link census
+    LinkSet ls;
+    TmpBuf<uint32_t> cell;
+    TmpBuf<unsigned long long> lc;
+    unsigned long long cv[LC_N];
+    TRY(link_set(h, st, fl, ls));
+    if (lt_env("PSIM_LAT_CELL", "cell")) {
+        TRY(cell.ensure(N, -1));
+        k_lt_cell<<<grid_for(N), BLK, 0, st>>>(seed, N, cell.p);
+    }
+    TRY(lc.alloc_on(LC_N, st));
+    TRY(lt_census(st, ls.ln, N, fl, cell.p, seed, lc.p, cv));
+    out->n_up = cv[LC_NUP]; out->links = cv[LC_LINKS]; out->link_cost_sum = cv[LC_COST];
+    out->link_nodes = cv[LC_NODES]; out->worst_sum = cv[LC_WORST]; out->best_sum = cv[LC_BEST];
+    for (int k = 0; k < PSIM_HIST_BINS; k++) out->link_cost[k] = cv[LC_HIST + k];
+    uint8_t rf = 0;
+    if (tree) TRY(read_back(st, &rf, fl + tree_root));
+    out->tree_root_live = (rf & F_UP) ? 1 : 0;
+    if (!ns && !out->tree_root_live) return PSIM_OK;
+    // 2. the sweeps from the sources, and one pass over the rows
+    const uint32_t cap = level_cap(max_sweeps);
+    LatRows b;
+    TRY(lt_alloc(st, N, cap, b));
+    if (ns) {
+        uint64_t live = 0;
+        TRY(lt_run(st, ls.ln, N, fl, cell.p, seed, b, src, ns, live, out->sweeps, out->truncated_mask,
+                   out->last_sweep));
+        out->live_mask = live;
+        out->sources_live = (uint64_t)__builtin_popcountll(live);
+        if (live) {
+            constexpr uint32_t PER_WAVE = 16;
+            TmpBuf<unsigned long long> lf;
+            unsigned long long fv[LF_N];
+            TRY(lf.alloc_on(LF_N, st));
+            k_lt_final<<<grid_for(((uint64_t)N + PER_WAVE - 1) / PER_WAVE * 64), BLK, 0, st>>>(b.cur.p, b.dsrc.p, fl, N,
+                                                                                               PER_WAVE, lf.p);
+            HIP_TRY(hipGetLastError());
+            TRY(read_back(st, fv, lf.p, LF_N));
+            for (uint32_t j = 0; j < PSIM_LAT_SOURCES; j++) {
+                out->reach[j] = fv[LF_REACH + j]; out->lat_sum[j] = fv[LF_SUM + j]; out->lat_ecc[j] = fv[LF_ECC + j];
+                out->pairs_reached += fv[LF_REACH + j]; out->lat_sum_all += fv[LF_SUM + j];
+                out->lat_max = std::max<uint64_t>(out->lat_max, fv[LF_ECC + j]);
+            }
+            for (int k = 0; k < PSIM_HIST_BINS; k++) out->lat[k] = fv[LF_HIST + k];
+            out->pairs_unreached = out->sources_live * (out->n_up - 1) - out->pairs_reached;
+        }
+    }
+    if (!out->tree_root_live) return PSIM_OK;
+    // 3. the tree half: T, its link costs, the one-slot sweeps over T and over L
+    TreeSet ts;
+    TmpBuf<uint32_t> dt, dl;
+    TmpBuf<unsigned long long> lr;
+    unsigned long long rv[LR_N];
+    uint64_t live = 0, sweeps = 0, trunc_t = 0, trunc_l = 0;
+    TRY(tree_set(h, st, fl, tree_root, ts));
+    const Links T = ts.csr.links();
+    TRY(lt_census(st, T, N, fl, cell.p, seed, lc.p, cv));
+    out->tree_links = cv[LC_LINKS]; out->tree_link_cost_sum = cv[LC_COST];
+    TRY(dt.ensure(N, -1)); TRY(dl.ensure(N, -1)); TRY(lr.alloc_on(LR_N, st));
+    TRY(lt_run(st, T, N, fl, cell.p, seed, b, &tree_root, 1, live, out->tree_sweeps, trunc_t, nullptr));
+    k_lt_column<<<grid_for(N), BLK, 0, st>>>(b.cur.p, N, dt.p);
+    TRY(lt_run(st, ls.ln, N, fl, cell.p, seed, b, &tree_root, 1, live, sweeps, trunc_l, nullptr));
+    k_lt_column<<<grid_for(N), BLK, 0, st>>>(b.cur.p, N, dl.p);
+    k_lt_tree<<<grid_for(N), BLK, 0, st>>>(dt.p, dl.p, fl, N, tree_root, lr.p);
+    HIP_TRY(hipGetLastError());
+    TRY(read_back(st, rv, lr.p, LR_N));
+    out->tree_reached = rv[LR_TREACH]; out->tree_lat_sum = rv[LR_TSUM]; out->tree_lat_max = rv[LR_TMAX];
+    out->overlay_reached = rv[LR_OREACH]; out->both_reached = rv[LR_BOTH];
+    out->tree_lat_sum_both = rv[LR_TSUMB]; out->overlay_lat_sum_both = rv[LR_OSUMB];
+    out->slower = rv[LR_SLOWER]; out->faster = rv[LR_FASTER];
+    out->tree_truncated = trunc_t || trunc_l ? 1 : 0;
     return PSIM_OK;
 }

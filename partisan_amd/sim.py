@@ -449,6 +449,29 @@ class Simulator(_Driver):
             out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
         return out
 
+    def latency_metrics(self, sources=None, k=64, seed=0, tree_root=None, max_sweeps=0):
+        """Link costs and the cheapest paths by latency from up to 64 sources
+        (psim_latency_metrics) as a dict of ints / arrays; a collective on
+        rank handles.  The sources are picked as graph_metrics() picks them
+        (the same k and seed give the same ids); an empty list with no
+        tree_root fills the link census only.  tree_root adds the tree half of
+        that Plumtree root."""
+        if sources is None:
+            rng = np.random.Generator(np.random.PCG64([seed, 0x6d]))
+            sources = rng.choice(self.n, size=min(k, self.n), replace=False)
+        src = np.ascontiguousarray(sources, np.uint32).reshape(-1)
+        root = NONE if tree_root is None else int(tree_root)
+        m = _abi.PsimLatencyMetrics()
+        self._check(self._extra["get_latency_metrics"](self._h, _abi.u32p(src) if src.size else None, src.size,
+                                                       root, max_sweeps, C.byref(m)), "get_latency_metrics")
+        out = {}
+        for name, _ in _abi.PsimLatencyMetrics._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(m, name)
+            out[name] = np.array(v[:], np.uint64) if hasattr(v, "__len__") else int(v)
+        return out
+
     def resilience(self, sources, thresholds, salts=None, fail_seed=0, max_levels=0):
         """Reach of a flood under up to 64 failure cases (psim_resilience) as
         a dict of ints / arrays; a collective on rank handles.  Case j floods
