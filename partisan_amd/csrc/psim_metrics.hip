@@ -174,6 +174,11 @@ __global__ void k_cc_init(const uint8_t* __restrict__ flags, uint32_t n, uint32_
 }
 
 // (the rows may be unfiltered: psim_get_histograms hands over the gathered active rows)
+// Hooks roots, not labels: the two ends' trees are followed to their roots
+// and the larger root is put under the smaller.  L[x] <= x always and a word
+// only ever falls, so L stays a forest; a root another thread lowered in the
+// meantime keeps the lower of the two (the link lost that way is found again:
+// `changed` is set, and the loop ends only after a pass that changed nothing)
 __global__ void k_cc_hook(Links ln, const uint8_t* __restrict__ flags, uint32_t n, uint32_t* L, uint32_t* changed) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !(flags[i] & F_UP)) return;
@@ -181,18 +186,37 @@ __global__ void k_cc_hook(Links ln, const uint8_t* __restrict__ flags, uint32_t 
     for (uint32_t k = 0, c = ln.cnt[i]; k < c; k++) {
         const uint32_t p = row[k];
         if (p == i || p >= n || !(flags[p] & F_UP)) continue;
-        const uint32_t a = L[i], b = L[p];
-        if (a < b) { if (atomicMin(&L[p], a) > a) *changed = 1; }
-        else if (b < a) { if (atomicMin(&L[i], b) > b) *changed = 1; }
+        uint32_t a = L[i], b = L[p];
+        if (a == b) continue;                         // (one parent: one tree)
+        while (L[a] != a) a = L[a];
+        while (L[b] != b) b = L[b];
+        if (a == b) continue;
+        const uint32_t lo = min(a, b), hi = max(a, b);
+        atomicMin(&L[hi], lo);
+        *changed = 1;
     }
 }
 
+// Every live node to its root.  A hook pass can leave a chain as deep as the
+// overlay is long (a path whose ids fall along it: j under j - 1 for every j),
+// and a thread that walked it alone would read the whole chain: n * depth
+// loads a pass.  So a node publishes each ancestor it reaches as its own
+// parent at once, and a walk that comes by takes the other's progress as its
+// next step: threads that advance together double their reach a step, as
+// pointer jumping does, without a launch a round.  A word only ever moves to
+// an ancestor of its node, so any mix of old and new reads ends at the root.
+// The passes of cc_run are few (logarithmic when the hooks halve the roots);
+// the work of one is n log(depth) loads at best and n * depth at worst
 __global__ void k_cc_jump(uint32_t n, uint32_t* L) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || L[i] == PSIM_NONE) return;
     uint32_t r = L[i];
-    while (L[r] != r) r = L[r];
-    L[i] = r;
+    for (;;) {
+        const uint32_t g = __atomic_load_n(&L[r], __ATOMIC_RELAXED);
+        if (g == r) break;
+        r = g;
+        __atomic_store_n(&L[i], r, __ATOMIC_RELAXED);
+    }
 }
 
 __global__ void k_cc_count(const uint32_t* __restrict__ L, uint32_t n, uint32_t* size, unsigned long long* comps) {
@@ -1766,19 +1790,29 @@ static int read_back(hipStream_t st, T* dst, const T* src, size_t n = 1) {
 }
 
 // weakly connected components of the live nodes over the rows k_cc_hook
-// reads: label propagation to a fixed point, then the component count and the
-// largest (comps, largest: zeroed device words; L, size: n words, size zeroed)
+// reads: root hooking and pointer jumping to a fixed point, then the component
+// count and the largest (comps, largest: zeroed device words; L, size: n
+// words, size zeroed).  A pass that hooks nothing ends the loop: every link
+// then joins two nodes of one tree, and a tree never leaves its component.
+// Every other pass takes at least one root away (the larger root of a link
+// between two trees gets a parent, and no node ever becomes a root again), so
+// n passes are the most there can be.  Running out of the bound is an error,
+// never a count (the getter's time on a path of 12 500 nodes whose ids run
+// against it: profiles/synthetic_overlays/cc_before.txt)
 static int cc_run(Links ln, const uint8_t* fl, uint32_t n, uint32_t* L, uint32_t* size, uint32_t* flag,
                   unsigned long long* comps, unsigned long long* largest, hipStream_t st) {
     k_cc_init<<<grid_for(n), BLK, 0, st>>>(fl, n, L);
-    for (int it = 0; it < 4096; it++) {
-        uint32_t changed = 0;
+    uint32_t changed = 1;
+    for (uint64_t it = 0; changed && it < (uint64_t)n + 2; it++) {
         HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
         k_cc_hook<<<grid_for(n), BLK, 0, st>>>(ln, fl, n, L, flag);
         k_cc_jump<<<grid_for(n), BLK, 0, st>>>(n, L);
         TRY(read_back(st, &changed, flag));
-        if (!changed) break;
     }
+    // (unreachable: the bound above cannot run out.  Were it to, on a ranked
+    // handle this return would come before the caller's next collective and
+    // leave the other ranks waiting in it)
+    if (changed) return PSIM_ESTATE;
     k_cc_count<<<grid_for(n), BLK, 0, st>>>(L, n, size, comps);
     k_cc_max<<<grid_for(n), BLK, 0, st>>>(size, n, largest);
     HIP_TRY(hipGetLastError());
